@@ -20,7 +20,19 @@ torch.distributed.run, before any GPU call) and refuses to run when fewer than
 N GPUs are visible, unless --allow-shared is given (a rehearsal of N ranks on
 fewer GPUs; the line then says so).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bunny15|cbox|c5]
+A plain run sets up, warms up, times the steps and prints the result line
+(value, ms_per_step and the timed steps' per-kernel HIP-event times).  --full
+adds the legs that take runs of their own after the timed region: the
+instrumented pass behind the roofline figures and the committed PMC sets they
+quote, the parity leg against the CPU oracle, the CPU baseline and, for N > 1
+ranks, the check of the assembled frame against a whole-frame render
+(--no-count, --no-parity and --no-cpu drop single legs of a --full run).
+--dump-outputs DIR writes the ImageBlock of the timed steps' last frame
+(rank 0: the frame assembled from every rank's tiles) as DIR/imageblock.npy,
+float32 [H + 2b, W + 2b, 5]; the scene, the frame and the counter-mode random
+numbers are the same from run to run.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bunny15|cbox|c5] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -109,8 +121,13 @@ def parse():
     ap.add_argument("--batch-paths", type=int, default=0)
     ap.add_argument("--finish-paths", type=int, default=-1,
                     help="tail-mode threshold (paths; 0 = off; default: the library's, mtsg_set_finish_paths)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-parity", action="store_true", help="skip the headline parity leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline's instrumented pass (and quote the committed "
+                         "PMC sets), the parity leg, the CPU baseline and, for N > 1 ranks, the assembly check")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the ImageBlock of the timed steps' last frame to DIR/imageblock.npy (float32; rank 0)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the headline parity leg")
     ap.add_argument("--parity-stride", type=int, default=8,
                     help="parity leg: compare the 16x16 tiles t %% N == 0 (1/N of the frame) at full spp")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time")
@@ -121,7 +138,7 @@ def parse():
                          "times (mtsg_set_tile_list); 0 = the fixed stride deal")
     ap.add_argument("--save", default="", help="write the developed image (.npy) here (rank 0)")
     ap.add_argument("--no-count", action="store_true",
-                    help="skip the instrumented (untimed) pass of per-ray counts (profiler runs)")
+                    help="--full: skip the instrumented (untimed) pass of per-ray counts (profiler runs)")
     ap.add_argument("--print-pmc-key", action="store_true", help="print this configuration's PMC key and exit")
     ap.add_argument("--pmc-pass", action="store_true",
                     help="profiler pass (tools/gpu_pmc_config.sh): render only this configuration's frame -- share 0 "
@@ -142,7 +159,10 @@ def parse():
                          "kdIntersectionCost, kdTraversalCost, kdEmptySpaceBonus, kdStopPrims, ...; measurement)")
     ap.add_argument("--shade-generic", action="store_true",
                     help="shade with the all-materials kernel instead of the scene's material set (A/B measurement)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def visible_gpus():
@@ -629,7 +649,7 @@ def main():
         # per frame, so bytes and time come from one profiler on the same
         # kernels; HIP events bracket short kernels loosely, round-3 VERDICT
         # weak #6); this run's HIP-event time is reported beside it
-        pj, psrc = pmc_lookup(pmc_key(a, world))
+        pj, psrc = pmc_lookup(pmc_key(a, world)) if a.full else (None, None)
         if pj:
             fam_ms = {"k_shade": kernels["shade_ms"], "k_finish": kernels["finish_ms"],
                       "k_camera": kernels["camera_ms"], "k_splat": kernels["splat_ms"]}
@@ -653,7 +673,7 @@ def main():
                                 "tcc_hit_rate": hits[0] if len(hits) == 1 else None}
             kernels["pmc"] = pmc
             kernels["pmc_source"] = psrc
-    if rank == 0 and not a.no_count:
+    if rank == 0 and a.full and not a.no_count:
         # instrumented pass at reduced spp (per-ray counts are spp-independent)
         pc = params.copy()
         pc.spp = max(1, min(params.spp, 16))
@@ -749,8 +769,14 @@ def main():
         keys = None if cur["keys"] is None else cur["keys"].copy()
         part = ("win", host_win[:nw[0]].copy(), keys) if nw else ("block", host_block.copy(), None)
         frame = gather_frame(pg, rank, world, part, params.tile_w, params.tile_h, border)
+    if rank == 0 and a.dump_outputs:
+        # what a caller of the timed path receives: the frame's ImageBlock
+        # (with emulated shares: the whole frame of the last whole-frame step)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "imageblock.npy"),
+                np.ascontiguousarray(host_block if frame is None else frame, dtype=np.float32))
     use_whole()
-    if rank == 0 and world > 1:
+    if rank == 0 and world > 1 and a.full:
         # the assembled frame vs the whole frame rendered by rank 0's GPU alone
         # (global RNG keys: the same samples; the film's float additions may
         # run in another order)
@@ -766,10 +792,10 @@ def main():
                     "tiles_per_rank": counts.tolist()}
     if rank == 0 and a.save and frame is not None:
         np.save(a.save, mtsg.develop(frame[border:H - border, border:W - border]))
-    if rank == 0 and frame is not None and not a.no_parity:
+    if rank == 0 and frame is not None and a.full and not a.no_parity:
         parity = parity_at_headline(scene, frame, params, border, a.parity_stride, world)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu:
         cpu = cpu_baseline(scene, params, border, a.cpu_seconds)
 
     gpu.free(film)

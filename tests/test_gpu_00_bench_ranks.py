@@ -2,8 +2,9 @@
 launcher it starts its own N ranks (torch.distributed.run, one process per
 GPU), refuses more ranks than visible GPUs, and with --allow-shared (a
 rehearsal of N ranks on one GPU) gathers every rank's tile ImageBlocks to
-rank 0, checks the assembled frame against a whole-frame render and runs the
-parity leg on it.  This file runs first among the GPU tests (its name sorts
+rank 0 and, under --full, checks the assembled frame against a whole-frame
+render and runs the parity leg on it; a plain run only times its steps and
+can dump its last frame (--dump-outputs).  This file runs first among the GPU tests (its name sorts
 first) and never initialises the GPU in the pytest process itself: the ranks
 are child processes, and a process that has initialised the GPU must not
 start programs (the device count here comes from torch, which does not
@@ -31,7 +32,7 @@ SMALL = ["--workload", "cbox", "--width", "320", "--height", "180", "--spp", "16
 
 
 def test_bench_two_ranks_gather_and_check_the_frame():
-    r = _bench(["--gpus", "2", "--allow-shared", *SMALL])
+    r = _bench(["--gpus", "2", "--allow-shared", "--full", *SMALL])   # --full: the assembly check and the parity leg
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [line for line in r.stdout.splitlines() if line.startswith("{")]
     assert len(lines) == 1, r.stdout[-3000:]
@@ -41,6 +42,31 @@ def test_bench_two_ranks_gather_and_check_the_frame():
     assert out["assembly"]["pass"], out["assembly"]
     assert out["parity"]["pass"], out["parity"]
     assert "assembled from all 2 ranks" in out["parity"]["tiles"]
+
+
+def test_plain_run_times_its_steps_and_dumps_the_frame(tmp_path):
+    """Without --full the run only times its steps (no roofline, parity or
+    CPU-baseline leg) and --dump-outputs writes the last frame's ImageBlock."""
+    import numpy as np
+    r = _bench(["--gpus", "1", "--dump-outputs", str(tmp_path / "out"), *SMALL], timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [line for line in r.stdout.splitlines() if line.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    # value = the frame's samples over one timed step's time; the line rounds
+    # ms_per_step to 0.01 ms (half a unit either way) and value to 0.001
+    ms = out["ms_per_step"]
+    assert out["value"] == pytest.approx(320 * 180 * 16 / (ms * 1e-3) / 1e6, rel=0.005 / (ms - 0.005) + 1e-4)
+    assert out["roofline"] is None and out["parity"] is None and out["cpu_baseline"] is None
+    assert out["kernels"]["frame_ms"] > 0 and "pmc" not in out["kernels"]
+    assert sorted(os.listdir(tmp_path / "out")) == ["imageblock.npy"]
+    block = np.load(tmp_path / "out" / "imageblock.npy")
+    assert block.dtype == np.float32 and block.ndim == 3 and block.shape[2] == 5
+    assert block.shape[0] > 180 and block.shape[1] > 320 and block.shape[0] - 180 == block.shape[1] - 320
+    b = (block.shape[0] - 180) // 2
+    weight = block[b:-b, b:-b, 4]
+    assert np.isfinite(block).all() and (weight > 0).all() and block[b:-b, b:-b, :3].mean() > 0
 
 
 @pytest.mark.skipif(bench.visible_gpus() >= 2, reason="needs a box with fewer than 2 GPUs")

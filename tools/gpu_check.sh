@@ -8,8 +8,8 @@ step() { local name=$1 lim=$2; shift 2; echo "== $name $(date +%T)"; timeout -k 
 for w in ${*:-tests bench inst e8}; do
   case $w in
     tests) step tests 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
-    bench) step bench 600 python bench.py --steps 10 --warmup 3 ;;
-    inst) step inst 300 python bench.py --steps 5 --warmup 2 --instancing two-level --no-cpu --no-parity ;;
-    e8) step e8 300 python bench.py --steps 10 --warmup 3 --emulate-ranks 8 --no-cpu --no-parity ;;
+    bench) step bench 600 python bench.py --full --steps 10 --warmup 3 ;;
+    inst) step inst 300 python bench.py --full --steps 5 --warmup 2 --instancing two-level --no-cpu --no-parity ;;
+    e8) step e8 300 python bench.py --full --steps 10 --warmup 3 --emulate-ranks 8 --no-cpu --no-parity ;;
   esac
 done

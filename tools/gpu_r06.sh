@@ -18,18 +18,18 @@ for w in ${*:-tests bench}; do
     tests-parity) step tests-parity 600 $PYT tests/test_gpu_parity.py tests/test_gpu_configs.py tests/test_gpu_c4.py ;;
     tests-inst) step tests-inst 600 $PYT tests/test_gpu_instancing.py tests/test_gpu_edge_rays.py tests/test_gpu_finish.py ;;
     vtests-*) v=${w#vtests-}; MTSG_LIB=$(lib $v) step $w 900 $PYT tests ;;
-    bench) step bench 600 python bench.py --steps 10 --warmup 3 ;;
+    bench) step bench 600 python bench.py --full --steps 10 --warmup 3 ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     # C3 with the instrumented pass (SIMD efficiency, iterations) / without it
-    cq-*) v=${w#cq-}; MTSG_LIB=$(lib $v) step $w 300 python bench.py --steps 10 --warmup 3 $Q ;;
+    cq-*) v=${w#cq-}; MTSG_LIB=$(lib $v) step $w 300 python bench.py --full --steps 10 --warmup 3 $Q ;;
     q-*) v=${w#q-}; MTSG_LIB=$(lib $v) step $w 300 python bench.py --steps 10 --warmup 3 $Q --no-count ;;
-    iq-*) v=${w#iq-}; MTSG_LIB=$(lib $v) step $w 300 python bench.py --steps 5 --warmup 2 --instancing two-level $Q ;;
+    iq-*) v=${w#iq-}; MTSG_LIB=$(lib $v) step $w 300 python bench.py --full --steps 5 --warmup 2 --instancing two-level $Q ;;
     c5q-*) v=${w#c5q-}; MTSG_LIB=$(lib $v) step $w 600 python bench.py --steps 3 --warmup 1 --workload c5 --width 1920 --height 1080 --spp 1024 $Q --no-count ;;
     # the shading event sort A/B, both in append order
     ssq-*) v=${w#ssq-}; MTSG_LIB=$(lib $v) step $w 300 python bench.py --steps 10 --warmup 3 $Q --no-count --ray-order 0 ;;
     ssc5-*) v=${w#ssc5-}; MTSG_LIB=$(lib $v) step $w 600 python bench.py --steps 3 --warmup 1 --workload c5 --width 1920 --height 1080 --spp 1024 $Q --no-count --ray-order 0 ;;
     ssc2-*) v=${w#ssc2-}; MTSG_LIB=$(lib $v) step $w 300 python bench.py --steps 5 --warmup 2 --workload cbox $Q --no-count --ray-order 0 ;;
-    qro0) step qro0 300 python bench.py --steps 10 --warmup 3 $Q --ray-order 0 ;;
+    qro0) step qro0 300 python bench.py --full --steps 10 --warmup 3 $Q --ray-order 0 ;;
     c5ro0) step c5ro0 600 python bench.py --steps 3 --warmup 1 --workload c5 --width 1920 --height 1080 --spp 1024 $Q --no-count --ray-order 0 ;;
     e8bands*) step $w 300 python bench.py --steps 5 --warmup 2 --emulate-ranks 8 $Q --no-count --share-layout bands --balance-rounds 6 ;;
     e8spread*) step $w 300 python bench.py --steps 5 --warmup 2 --emulate-ranks 8 $Q --no-count --balance-rounds 6 ;;
@@ -59,13 +59,13 @@ for w in ${*:-tests bench}; do
     ranks)
       # the launcher path (as the driver runs it) and the self-launching path,
       # two ranks on this one GPU; then the refusal without --allow-shared
-      step ranks-torchrun 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu --allow-shared
-      step ranks-self 600 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu --allow-shared
-      echo "== ranks-refuse"; timeout -k 10 300 python bench.py --gpus 2 --steps 1 --warmup 0 --no-cpu > $O/ranks-refuse.log 2>&1; echo "ranks-refuse rc=$? (non-zero expected)"; tail -n 2 $O/ranks-refuse.log ;;
-    c5) step c5 600 python bench.py --steps 3 --warmup 1 --workload c5 --width 1920 --height 1080 --spp 1024 ;;
-    c2) step c2 600 python bench.py --steps 5 --warmup 2 --workload cbox ;;
-    inst) step inst 300 python bench.py --steps 5 --warmup 2 --instancing two-level --no-cpu --no-parity ;;
-    e8) step e8 300 python bench.py --steps 5 --warmup 2 --emulate-ranks 8 --no-cpu --no-parity ;;
+      step ranks-torchrun 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu --allow-shared
+      step ranks-self 600 python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu --allow-shared
+      echo "== ranks-refuse"; timeout -k 10 300 python bench.py --full --gpus 2 --steps 1 --warmup 0 --no-cpu > $O/ranks-refuse.log 2>&1; echo "ranks-refuse rc=$? (non-zero expected)"; tail -n 2 $O/ranks-refuse.log ;;
+    c5) step c5 600 python bench.py --full --steps 3 --warmup 1 --workload c5 --width 1920 --height 1080 --spp 1024 ;;
+    c2) step c2 600 python bench.py --full --steps 5 --warmup 2 --workload cbox ;;
+    inst) step inst 300 python bench.py --full --steps 5 --warmup 2 --instancing two-level --no-cpu --no-parity ;;
+    e8) step e8 300 python bench.py --full --steps 5 --warmup 2 --emulate-ranks 8 --no-cpu --no-parity ;;
     stats-c3) step stats-c3 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o c3 -- python3 bench.py --steps 5 --warmup 2 --no-cpu --no-parity --no-count ;;
     stats-c5) step stats-c5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c5 -o c5 -- python3 bench.py --steps 2 --warmup 1 --workload c5 --width 1920 --height 1080 --spp 1024 --no-cpu --no-parity --no-count ;;
     # per-launch kernel durations of one frame (tools/launch_times.py)

@@ -11,12 +11,12 @@ step() { local name=$1 lim=$2; shift 2; echo "== $name $(date +%T)"; timeout -k 
 for w in $WHAT; do
   case $w in
     tests) step tests 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
-    bench) step bench 600 python bench.py --steps 10 --warmup 3 ;;
+    bench) step bench 600 python bench.py --full --steps 10 --warmup 3 ;;
     prof)
-      step stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats -- python bench.py --no-cpu --no-parity
-      step fetch 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O -o fetch -- python bench.py --no-cpu --no-parity --steps 1 --warmup 0
-      step write 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O -o write -- python bench.py --no-cpu --no-parity --steps 1 --warmup 0
-      step tcc 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $O -o tcc -- python bench.py --no-cpu --no-parity --steps 1 --warmup 0
+      step stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats -- python bench.py --full --no-cpu --no-parity
+      step fetch 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O -o fetch -- python bench.py --full --no-cpu --no-parity --steps 1 --warmup 0
+      step write 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O -o write -- python bench.py --full --no-cpu --no-parity --steps 1 --warmup 0
+      step tcc 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $O -o tcc -- python bench.py --full --no-cpu --no-parity --steps 1 --warmup 0
       python tools/traffic_summary.py $O > $O/traffic.json && cat $O/traffic.json
       python tools/tcc_summary.py $O > $O/tcc.json && cat $O/tcc.json ;;
   esac

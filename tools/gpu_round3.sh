@@ -11,12 +11,12 @@ step() { local name=$1 lim=$2; shift 2; echo "== $name $(date +%T)"; timeout -k 
 for w in ${*:-tests bench inst e8}; do
   case $w in
     tests) step tests 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread ;;
-    kd) step kd 300 python bench.py --steps 5 --warmup 2 --kd-build device --no-cpu --no-parity ;;
-    bench) step bench 600 python bench.py --steps 10 --warmup 3 ;;
-    inst) step inst 300 python bench.py --steps 5 --warmup 2 --instancing two-level --no-cpu --no-parity ;;
-    e8) step e8 300 python bench.py --steps 5 --warmup 2 --emulate-ranks 8 --no-cpu --no-parity ;;
-    c5) step c5 600 python bench.py --steps 3 --warmup 1 --workload c5 --width 1920 --height 1080 --spp 1024 ;;
-    c2) step c2 600 python bench.py --steps 5 --warmup 2 --workload cbox ;;
+    kd) step kd 300 python bench.py --full --steps 5 --warmup 2 --kd-build device --no-cpu --no-parity ;;
+    bench) step bench 600 python bench.py --full --steps 10 --warmup 3 ;;
+    inst) step inst 300 python bench.py --full --steps 5 --warmup 2 --instancing two-level --no-cpu --no-parity ;;
+    e8) step e8 300 python bench.py --full --steps 5 --warmup 2 --emulate-ranks 8 --no-cpu --no-parity ;;
+    c5) step c5 600 python bench.py --full --steps 3 --warmup 1 --workload c5 --width 1920 --height 1080 --spp 1024 ;;
+    c2) step c2 600 python bench.py --full --steps 5 --warmup 2 --workload cbox ;;
     pmc-c3) bash tools/gpu_pmc_config.sh r03 c3 || exit $? ;;
     pmc-inst) bash tools/gpu_pmc_config.sh r03 c3_two_level --instancing two-level || exit $? ;;
     pmc-c5) bash tools/gpu_pmc_config.sh r03 c5 --workload c5 --width 1920 --height 1080 --spp 1024 || exit $? ;;
