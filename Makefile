@@ -23,7 +23,7 @@ ORACLE      := oracle/liboracle.so
 ORACLE_FAST := oracle/liboracle_fast.so
 
 .PHONY: all host device oracle clean
-all: host device oracle $(PATH_LIB) $(CLI) scenes/sky512.pfm tools/math_probe tools/math_bench tools/div_probe tools/check_glibc_mathf tools/check_env_guide
+all: host device oracle $(PATH_LIB) $(CLI) scenes/sky512.pfm tools/math_probe tools/math_bench tools/div_probe tools/check_glibc_mathf tools/check_env_guide tools/check_multichannel_host
 host: $(HOST_LIB)
 device: $(DEV_LIB)
 oracle: $(ORACLE) $(ORACLE_FAST)
@@ -50,19 +50,26 @@ DEV_FLAGS := -O3 -std=c++17 -fPIC -Wall -ffp-contract=off -fno-slp-vectorize -mu
 # -0.6%; the two-level kernel in mtsg.hip loses 3% under it: DESIGN §3)
 DEV_FLAT_FLAGS ?= -mllvm -amdgpu-sched-strategy=max-memory-clause
 DEV_OBJ   ?= build/dev
-DEV_OBJS  := $(DEV_OBJ)/mtsg.o $(DEV_OBJ)/trace_flat.o $(DEV_OBJ)/kdbuild.o $(foreach k,0 1 2 3 4,$(DEV_OBJ)/smp_$(k).o)
+DEV_OBJS  := $(DEV_OBJ)/mtsg.o $(DEV_OBJ)/trace_flat.o $(DEV_OBJ)/fields.o $(DEV_OBJ)/kdbuild.o $(foreach k,0 1 2 3 4,$(DEV_OBJ)/smp_$(k).o)
 $(DEV_OBJ)/mtsg.o: $(PKG)/csrc/mtsg.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
 $(DEV_OBJ)/trace_flat.o: $(PKG)/csrc/trace_flat.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_FLAT_FLAGS) $(DEV_EXTRA) -c -o $@ $<
+# the multichannel integrator's field kernel and block splats (fields.hip)
+$(DEV_OBJ)/fields.o: $(PKG)/csrc/fields.hip $(DEV_HDR)
+	@mkdir -p $(DEV_OBJ)
+	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
 $(DEV_OBJ)/kdbuild.o: $(PKG)/csrc/kdbuild.hip include/mtsg.h
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
 $(DEV_OBJ)/smp_%.o: $(PKG)/csrc/smp_kernels.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -DMTSG_TU_SAMPLER=$* $(if $(filter 0,$*),-DMTSG_TU_OCCUPANCY) -c -o $@ $<
+# the objects are intermediates: a tree that carries the library without them
+# (a copy that leaves object files out) is current, not stale
+.SECONDARY: $(DEV_OBJS)
 $(DEV_LIB): $(DEV_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(DEV_OBJS)
 
@@ -99,6 +106,12 @@ tools/check_glibc_mathf: tools/check_glibc_mathf.cpp $(PKG)/csrc/glibc_mathf.h
 # the device's guided envmap CDF searches against std::lower_bound, on the host
 tools/check_env_guide: tools/check_env_guide.cpp $(PKG)/csrc/envmap.h $(HOST_LIB)
 	$(HIPCC) -O2 -std=c++17 -ffp-contract=off -Iinclude -o $@ $< -L$(PKG) -lmtsg_host -Wl,-rpath,'$$ORIGIN/../$(PKG)'
+
+# the host side of a multichannel scene (load, descriptor, develop, EXR) as a
+# stand-alone program compiled with the host sources under ASan + UBSan (CPU only)
+tools/check_multichannel_host: tools/check_multichannel_host.cpp $(HOST_SRC) $(HOST_HDR) $(SOBOL_BIN)
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall \
+	    -DMTSH_SOBOL_BIN='"$(SOBOL_BIN)"' -o $@ $< $(HOST_SRC) -lz -lpthread
 
 # synthetic HDR environment for the envmap scenes (tools/gen_envmap.py)
 scenes/sky512.pfm: tools/gen_envmap.py

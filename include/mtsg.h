@@ -760,6 +760,92 @@ int  mtsg_trace_shadow(mtsg_scene *scene, uint32_t n, const float *rays,
 int  mtsg_render_samples(mtsg_scene *scene, const mtsg_render_params *params,
                          float *L_out);
 
+/* ---- multichannel / field integrators (AOV channels) ----------------------
+ * Mitsuba's `multichannel` integrator (src/integrators/misc/multichannel.cpp:
+ * 87-243) with `path` and `field` children (src/integrators/misc/field.cpp:
+ * 55-187).  Per camera sample the camera ray is intersected once and every
+ * child returns one spectrum from that intersection record
+ * (multichannel.cpp:205-214); the ImageBlock texel is
+ *   [spec_0 .. spec_{m-1}, alpha, weight]  = 3m + 2 floats
+ * (multichannel.cpp:143-145,207-217), alpha 1 on a hit and 0 on a miss
+ * (records.inl:124-137).  The blocks are created with warn = false, so no
+ * sample is rejected (imageblock.h:147-151): negative and non-finite values
+ * are put as they are.  `field` children draw no random numbers, so the
+ * `path` child's samples are those of the plain `path` render, bit for bit.
+ * The descriptor travels beside the scene descriptor, whose layout it leaves
+ * alone; mtsh_scene_aov builds it. */
+#define MTSG_MAX_SUBINTEGRATORS 8
+enum {
+    MTSG_AOV_PATH          = 0,   /* the `path` child (at most one)            */
+    MTSG_FIELD_POSITION    = 1,   /* its.p                                     */
+    MTSG_FIELD_REL_POSITION = 2,  /* world_to_camera applied to its.p          */
+    MTSG_FIELD_DISTANCE    = 3,   /* its.t in all three channels               */
+    MTSG_FIELD_GEO_NORMAL  = 4,   /* its.geoFrame.n                            */
+    MTSG_FIELD_SH_NORMAL   = 5,   /* its.shFrame.n                             */
+    MTSG_FIELD_UV          = 6,   /* (its.uv.x, its.uv.y, 0)                   */
+    MTSG_FIELD_ALBEDO      = 7,   /* its.shape->getBSDF()->getDiffuseReflectance(its) */
+    MTSG_FIELD_SHAPE_INDEX = 8,   /* position of its.shape in Scene::m_shapes, or -1 */
+    MTSG_FIELD_PRIM_INDEX  = 9    /* its.primIndex                             */
+};
+typedef struct mtsg_aov_child {
+    int32_t kind;                 /* MTSG_AOV_PATH or MTSG_FIELD_*             */
+    float undefined[3];           /* field: the value of a miss (field.cpp:96-104) */
+} mtsg_aov_child;
+/* getDiffuseReflectance of one mtsg_bsdf record: `factor` when !textured,
+ * else the record's texture (unfiltered: the record carries no UV partials,
+ * mtsg_tex_eval with duv == NULL) times `factor`.  diffuse: the reflectance
+ * (diffuse.cpp:106-108); plastic: diffuseReflectance * (1 - fdrExt)
+ * (plastic.cpp:219-221); roughplastic: diffuseReflectance * Ftr
+ * (roughplastic.cpp:309-320); conductors and dielectrics: 0 (bsdf.cpp:82-86).
+ * A twosided front record picks its back record when !(wi.z > 0)
+ * (twosided.cpp:198-203). */
+typedef struct mtsg_aov_bsdf {
+    float factor[3];
+    int32_t textured;
+} mtsg_aov_bsdf;
+/* One mtsg_shape in Mitsuba's terms: scene_index is the position in
+ * Scene::m_shapes (scene.cpp:345-357,608-647) of the shape's first element,
+ * -1 for instanced geometry (its.shape is the group's mesh, which is not in
+ * the list).  A mesh loaded from a compound shape (an `obj` with several
+ * groups) holds elem_count elements: element e starts at the mesh's local
+ * triangle elem_starts[elem_offset + e], has scene index scene_index + e, and
+ * its triangles' primIndex counts from its own start (skdtree.h:418). */
+typedef struct mtsg_aov_shape {
+    int32_t scene_index;
+    uint32_t elem_offset, elem_count;
+    uint32_t pad;
+} mtsg_aov_shape;
+typedef struct mtsg_aov_desc {
+    uint32_t n_children;          /* 1 .. MTSG_MAX_SUBINTEGRATORS              */
+    uint32_t pad;
+    mtsg_aov_child children[MTSG_MAX_SUBINTEGRATORS];
+    float world_to_camera[16];    /* the sensor transform's inverse, row-major */
+    uint32_t n_bsdfs;             /* == the scene's n_bsdfs                    */
+    uint32_t n_shapes;            /* == the scene's n_shapes                   */
+    const mtsg_aov_bsdf *bsdfs;
+    const mtsg_aov_shape *shapes;
+    uint32_t n_elems;
+    uint32_t pad2;
+    const uint32_t *elem_starts;
+} mtsg_aov_desc;
+
+/* Activate (or, desc == NULL, remove) the multichannel child set of a scene
+ * handle.  The `uv` field and a textured albedo need the scene's tri_uv.
+ * While a set is active the single-film entries (mtsg_render,
+ * mtsg_render_device, mtsg_render_device_tiles, mtsg_render_samples) return
+ * MTSG_ERR_INVALID instead of dropping channels. */
+int  mtsg_scene_set_aov(mtsg_scene *scene, const mtsg_aov_desc *desc);
+
+/* The multichannel forms of mtsg_render / mtsg_render_device /
+ * mtsg_render_device_tiles: the same blocks and windows with 3m + 2 floats
+ * per texel.  MTSG_ERR_INVALID without an active set. */
+int  mtsg_render_multi(mtsg_scene *scene, const mtsg_render_params *params, float *block_out);
+int  mtsg_render_device_multi(mtsg_scene *scene, const mtsg_render_params *params, float *block_device);
+int  mtsg_render_device_tiles_multi(mtsg_scene *scene, const mtsg_render_params *params, float *windows_device);
+/* mtsg_render_samples with 3m + 1 floats per sample: the children's
+ * spectra, then alpha. */
+int  mtsg_render_samples_multi(mtsg_scene *scene, const mtsg_render_params *params, float *out);
+
 void mtsg_scene_destroy(mtsg_scene *scene);
 
 /* Copies the last error message of the calling thread. */

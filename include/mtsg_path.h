@@ -57,6 +57,14 @@ int mtsh_path_job_gpus(const mtsh_path_job *job);
 int mtsh_path_job_render(mtsh_path_job *job, const mtsg_render_params *params, float *rgbaw_out,
                          double *seconds_out);
 
+/* The same for a scene whose integrator is `multichannel` (the job uploads its
+ * child set with the scene): block_out holds 3m + 2 floats per texel
+ * (mtsg_render_multi), and the GPUs' blocks are summed like the 5-channel
+ * ones.  Such a job's mtsh_path_job_render returns MTSG_ERR_INVALID, as this
+ * call does for a plain scene's job.  The tile callback is the same. */
+int mtsh_path_job_render_multi(mtsh_path_job *job, const mtsg_render_params *params, float *block_out,
+                               double *seconds_out);
+
 /* Share balancing on (default) or off (equal runs every render); either
  * call forgets the last render's rates. */
 int mtsh_path_job_set_balance(mtsh_path_job *job, int on);

@@ -164,6 +164,14 @@ int32_t mtsh_scene_set_film(mtsh_builder *b, const char *plugin, const mtsh_prop
                             const char *rfilter, const mtsh_prop *rfilter_props, int32_t n_rfilter_props);
 int32_t mtsh_scene_set_sampler(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n_props);
 int32_t mtsh_scene_set_integrator(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n_props);
+/* The `multichannel` integrator (multichannel.cpp:87-243): its nested
+ * integrators are added first, in Mitsuba's order (`path`, at most one, and
+ * `field`, field.cpp:69-110; -> the child's position, or -1), then the parent
+ * is set, which takes the children added so far (props: multichannel's own,
+ * it reads none).  mtsh_scene_set_integrator("multichannel") does the same as
+ * the second call.  The film's pixelFormat must list one entry per child. */
+int32_t mtsh_scene_add_integrator_child(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n_props);
+int32_t mtsh_scene_set_multichannel(mtsh_builder *b, const mtsh_prop *props, int32_t n_props);
 /* The Scene's own Properties (Scene::Scene(props), scene.cpp:47-83; a
  * plugin passes scene->getProperties()): the build parameters of the scene's
  * kd-tree, kdIntersectionCost, kdTraversalCost, kdEmptySpaceBonus
@@ -207,6 +215,22 @@ void mtsh_set_instancing(int mode);
 
 const mtsg_scene_desc *mtsh_scene_desc(const mtsh_scene *scene);
 
+/* The multichannel descriptor of the scene (mtsg.h mtsg_aov_desc, for
+ * mtsg_scene_set_aov; owned by the scene), or NULL when its integrator is
+ * not `multichannel`. */
+const mtsg_aov_desc *mtsh_scene_aov(const mtsh_scene *scene);
+
+/* The film's pixelFormat entries and channel names (hdrfilm.cpp:216-295).
+ * formats (may be NULL) receives up to capacity MTSH_FORMAT_* ids, the count
+ * is returned.  mtsh_scene_film_channels writes the output channel names
+ * ("name.R" ...; "R" without channelNames) NUL-separated into buf (may be
+ * NULL) and returns their number, or -2 when buf_size is too small. */
+enum {
+    MTSH_FORMAT_LUMINANCE = 0, MTSH_FORMAT_LUMINANCE_ALPHA, MTSH_FORMAT_RGB, MTSH_FORMAT_RGBA, MTSH_FORMAT_XYZ, MTSH_FORMAT_XYZA
+};
+int mtsh_scene_film_formats(const mtsh_scene *scene, int32_t *formats, int capacity);
+int mtsh_scene_film_channels(const mtsh_scene *scene, char *buf, size_t buf_size);
+
 /* Integrator properties + sampleCount of the scene; tile = full film. */
 void mtsh_scene_render_params(const mtsh_scene *scene, mtsg_render_params *out);
 
@@ -236,6 +260,23 @@ int mtsh_scene_set_kdtree(mtsh_scene *scene, const mtsg_kdnode *nodes, uint32_t 
 
 /* hdrfilm develop (fmtconv.cpp:962-974): rgb = (sum w*L) / (sum w). */
 void mtsh_develop(const float *rgbaw, int w, int h, float *rgb_out);
+
+/* hdrfilm develop of a multichannel block
+ * (Bitmap::convertMultiSpectrumAlphaWeight, src/libcore/bitmap.cpp:1608-1673):
+ * block holds w * h texels of 3 * n_formats + 2 floats (the children's
+ * spectra, alpha, weight); every value is multiplied by 1 / weight (by 0
+ * where the weight is 0) and entry i converted to formats[i] (MTSH_FORMAT_*):
+ * luminance / XYZ by spectrum.cpp:229-234, alpha appended where the format
+ * has one.  out receives w * h * (sum of the formats' channel counts) floats,
+ * interleaved per texel.  Returns the channels per texel, -1 on error. */
+int mtsh_develop_multi(const float *block, int w, int h, const int32_t *formats, int n_formats, float *out);
+
+/* Write float planes as an OpenEXR scanline image, uncompressed, FLOAT
+ * channels with the given names (hdrfilm's multichannel output is EXR; PFM
+ * cannot hold it, hdrfilm.cpp:328-334).  data holds w * h texels of
+ * n_channels interleaved floats (mtsh_develop_multi's layout), rows
+ * top-down.  Returns 0 on success. */
+int mtsh_write_exr(const char *path, int w, int h, int n_channels, const char *const *names, const float *data);
 
 /* Write an RGB float image as PFM (bitmap.cpp:347-398). Returns 0 on success. */
 int mtsh_write_pfm(const char *path, int w, int h, const float *rgb);

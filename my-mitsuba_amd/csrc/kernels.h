@@ -227,6 +227,38 @@ struct FlatTraceLaunch {
 void launch_trace_flat(const FlatTraceLaunch &a);
 int trace_flat_blocks_per_cu();   // k_trace_s<false, 16> workgroups per CU (occupancy query)
 
+// multichannel / field integrators (fields.hip, its own translation unit):
+// the active child set of a scene handle (mtsg_scene_set_aov) and its SoA
+// field buffers.  Field child f writes plane c of its spectrum at
+// planes + (3 f + c) * cap, one float per sample slot of the batch.
+struct DevAov {
+    int m;                                     // children
+    int pathChild;                             // position of the `path` child, -1: fields only
+    int nf;                                    // field children
+    int kind[MTSG_MAX_SUBINTEGRATORS];         // MTSG_FIELD_* of field child f
+    int child[MTSG_MAX_SUBINTEGRATORS];        // its position among the children
+    float undef[MTSG_MAX_SUBINTEGRATORS][3];
+    float w2c[16];
+    const mtsg_aov_bsdf *bsdfs;
+    const mtsg_aov_shape *shapes;
+    const uint32_t *elems;
+    float *planes;
+    size_t cap;
+};
+struct FieldsLaunch {
+    hipStream_t stream;
+    const DevScene *S;
+    const DevCamera *C;
+    const DevIntegrator *I;
+    const DevBatch *B;
+    const DevPaths *P;
+    const DevAov *A;
+    float *film;
+    int blockW, blockH, win;
+};
+void launch_fields(const FieldsLaunch &a);        // k_fields: after the bounce-0 trace launch
+void launch_splat_multi(const FieldsLaunch &a);   // the `path` child (or alpha and weight alone), then the fields
+
 }  // namespace mtsg
 
 using namespace mtsg;
@@ -2778,6 +2810,20 @@ DEV void fill_its(const DevScene &S, float3 ro, float3 rd, float4 h, uint32_t in
     its.sh.t = cross(n, its.sh.s);
 }
 
+// its.uv of a hit: a triangle's barycentric sum of its vertices' texture
+// coordinates (skdtree.h:398-405; t0 / t1 = the first two words of its ttex
+// record), a rectangle's (rectangle.cpp:155-164).  Shared by the texture
+// lookups and the `uv` field (fields.hip).
+DEV float2 tri_uv(const float4 t0, const float4 t1, const float4 h) {
+#pragma clang fp contract(off)
+    const float bx = 1 - h.y - h.z, by = h.y, bz = h.z;
+    return make_float2(t0.x * bx + t0.z * by + t1.x * bz, t0.y * bx + t0.w * by + t1.y * bz);
+}
+DEV float2 rect_uv(const float4 h) {
+#pragma clang fp contract(off)
+    return make_float2(0.5f * (h.y + 1), 0.5f * (h.z + 1));
+}
+
 // `bitmap` texture value of a hit (Texture2D::eval(its, filter),
 // texture.cpp:112-121, over BitmapTexture::eval, bitmap.cpp:431-499, times
 // the ScaleTexture of ensureEnergyConservation).  The hit's uv and dpdv come
@@ -2797,8 +2843,7 @@ DEV float3 texture_eval(const DevScene &S, int tex, float4 h, uint32_t inst, con
     if (!(p & 0x80000000u)) {
         const float4 *t = S.ttex + 3 * (size_t)p;
         const float4 t0 = t[0], t1 = t[1], t2 = t[2];
-        const float bx = 1 - h.y - h.z, by = h.y, bz = h.z;
-        uv = make_float2(t0.x * bx + t0.z * by + t1.x * bz, t0.y * bx + t0.w * by + t1.y * bz);
+        uv = tri_uv(t0, t1, h);
         dpdv = mk3(t1.z, t1.w, t2.x);
         const float4 *rec = S.shrec + 6 * (size_t)p;
         const float4 r4 = rec[4], r5 = rec[5];
@@ -2813,7 +2858,7 @@ DEV float3 texture_eval(const DevScene &S, int tex, float4 h, uint32_t inst, con
         }
     } else {
         const mtsg_rect &r = S.rects[p & 0x7FFFFFFFu];
-        uv = make_float2(0.5f * (h.y + 1), 0.5f * (h.z + 1));
+        uv = rect_uv(h);
         dpdu = ld3(r.dpdu);
         dpdv = ld3(r.dpdv);
     }
@@ -3878,9 +3923,20 @@ constexpr int SPLAT_CHUNK = MTSG_SPLAT_CHUNK;   // samples per pixel per workgro
 // atomic per texel and channel into the HBM ImageBlock.
 // winSz > 0: film holds one winSz x winSz window (the tile and its border) per tile of
 // the call, window v = virtual tile v (mtsg_render_device_tiles)
-template <int K, int CH>
-__global__ void __launch_bounds__(BLOCK) k_splat(DevCamera C, DevIntegrator I, DevBatch B, DevPaths P, float *film, int blockW, int blockH,
-                                                 int winSz) {
+// The body is splat_tile, shared with the multichannel splats (fields.hip):
+// REJECT is the rejection rule of a warn = true ImageBlock (the plain `path`
+// film); MC selects the 3m + 2 float texel of the multichannel block, into
+// which a pass adds either the `path` child's spectrum with alpha and weight
+// (CH == 5, from P.L) or one field's spectrum (CH == 3, from its SoA planes).
+struct SplatMulti {
+    const float *src;   // field pass: plane c of the field at src + c * cap (one float per sample slot)
+    size_t cap;
+    int stride;         // floats per texel: 3m + 2
+    int coff;           // first float of the pass's spectrum in the texel; -1: none (alpha and weight only)
+};
+template <int K, int CH, bool REJECT, bool MC>
+DEV void splat_tile(const DevCamera &C, const DevIntegrator &I, const DevBatch &B, const DevPaths &P, float *film, int blockW,
+                    int blockH, int winSz, const SplatMulti &M) {
     __shared__ float acc[CH][LT * LT];
     constexpr int R = K / 2;
     for (int k = threadIdx.x; k < CH * LT * LT; k += BLOCK) (&acc[0][0])[k] = 0.0f;
@@ -3923,11 +3979,13 @@ __global__ void __launch_bounds__(BLOCK) k_splat(DevCamera C, DevIntegrator I, D
     if (inside) {
         for (uint32_t sl = sBeg; sl < sEnd; ++sl) {
             const uint32_t slot = ((uint32_t)tl * B.ns + sl) * (TILE * TILE) + pix;
-            const float4 L = ldS(&P.L[slot]);
+            float4 L;
+            if (MC && CH == 3) L = make_float4(M.src[slot], M.src[M.cap + slot], M.src[2 * M.cap + slot], 0.0f);
+            else L = ldS(&P.L[slot]);
             float ja, jb;
             camera_jitter(I, x, y, B.s0 + sl, ja, jb);
             // invalid samples are rejected (imageblock.h:147-151)
-            if (!(isfinite(L.x) && isfinite(L.y) && isfinite(L.z) && L.x >= 0 && L.y >= 0 && L.z >= 0)) continue;
+            if (REJECT && !(isfinite(L.x) && isfinite(L.y) && isfinite(L.z) && L.x >= 0 && L.y >= 0 && L.z >= 0)) continue;
             // sample position relative to the Mitsuba block origin
             // (imageblock.h:158-160)
             const float px = ((float)x + ja) - 0.5f - (float)mbx;
@@ -3953,7 +4011,7 @@ __global__ void __launch_bounds__(BLOCK) k_splat(DevCamera C, DevIntegrator I, D
                     for (int c = 0; c < K; ++c) {
                         const float w = wx[c] * wy[r];
 #pragma unroll
-                        for (int h = 0; h < CH; ++h) win[r][c][h] += w * v[CH == 5 ? h : (h == 3 ? 4 : h)];
+                        for (int h = 0; h < CH; ++h) win[r][c][h] += w * v[CH == 4 ? (h == 3 ? 4 : h) : h];
                     }
             }
         }
@@ -3973,21 +4031,40 @@ __global__ void __launch_bounds__(BLOCK) k_splat(DevCamera C, DevIntegrator I, D
     // one float per lane, so the lanes of a wave add to consecutive floats of
     // a texel row (4-5 64-B atomic requests per wave instruction, where one
     // texel per lane with its 5 channels strided 20 B apart touched ~20)
-    for (int j = threadIdx.x; j < LT * LT * 5; j += BLOCK) {
-        const int k = j / 5, h = j - 5 * k;
+    // FL floats of a texel per pass; the texel stride is 5, or 3m + 2 (MC)
+    constexpr int FL = MC ? CH : 5;
+    const int stride = MC ? M.stride : 5;
+    for (int j = threadIdx.x; j < LT * LT * FL; j += BLOCK) {
+        const int k = j / FL, h = j - FL * k;
         const int ty2 = k / LT, tx2 = k % LT;
         const int fx = x0 - MAX_BORDER + tx2 - (B.rect_x - bord), fy = y0 - MAX_BORDER + ty2 - (B.rect_y - bord);
         if (fx < 0 || fy < 0 || fx >= blockW || fy >= blockH) continue;
-        const float w = acc[CH - 1][k];
-        if (w == 0.0f) continue;
         // window texel (the filter's support ends at the border: outside it w == 0)
         const int wx = tx2 - (MAX_BORDER - bord), wy = ty2 - (MAX_BORDER - bord);
+        if (MC && CH == 3) {
+            // a field pass carries no weight: the texels the tile's filter support covers
+            if (wx < 0 || wy < 0 || wx >= TILE + 2 * bord || wy >= TILE + 2 * bord) continue;
+        } else {
+            if (acc[CH - 1][k] == 0.0f) continue;
+        }
         if (winSz && (wx < 0 || wy < 0 || wx >= winSz || wy >= winSz)) continue;
-        float *dst = winSz ? film + (((size_t)(B.tile0 + tl) * winSz + wy) * winSz + wx) * 5 : film + ((size_t)fy * blockW + fx) * 5;
-        // no alpha channel (CH == 4): alpha == 1 per sample, so its sum is the weight
-        const float v = h < 3 ? acc[h][k] : (h == 3 && CH == 5 ? acc[CH == 5 ? 3 : 0][k] : w);
-        unsafeAtomicAdd(dst + h, v);
+        float *dst = winSz ? film + (((size_t)(B.tile0 + tl) * winSz + wy) * winSz + wx) * stride
+                           : film + ((size_t)fy * blockW + fx) * stride;
+        if (MC) {
+            if (h < 3 && M.coff < 0) continue;
+            unsafeAtomicAdd(dst + (h < 3 ? M.coff + h : stride - 5 + h), acc[h][k]);
+        } else {
+            const float w = acc[CH - 1][k];
+            // no alpha channel (CH == 4): alpha == 1 per sample, so its sum is the weight
+            const float v = h < 3 ? acc[h][k] : (h == 3 && CH == 5 ? acc[CH == 5 ? 3 : 0][k] : w);
+            unsafeAtomicAdd(dst + h, v);
+        }
     }
+}
+template <int K, int CH>
+__global__ void __launch_bounds__(BLOCK) k_splat(DevCamera C, DevIntegrator I, DevBatch B, DevPaths P, float *film, int blockW, int blockH,
+                                                 int winSz) {
+    splat_tile<K, CH, true, false>(C, I, B, P, film, blockW, blockH, winSz, SplatMulti{nullptr, 0, 5, 0});
 }
 
 // zero the counters bounce b appends to (next-bounce paths qout, shadow rays

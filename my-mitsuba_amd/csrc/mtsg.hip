@@ -123,6 +123,18 @@ struct mtsg_scene {
     const uint32_t *sobolM = nullptr;        // sobol sampler tables (device)
     const uint64_t *sobolVdc = nullptr, *sobolVdcInv = nullptr;
     uint64_t sobolScramble = 0;
+    // multichannel / field integrators (mtsg_scene_set_aov; fields.hip): the
+    // active child set, its device tables, and the SoA field planes, which are
+    // allocated only while a set with fields is active
+    bool aovOn = false;
+    DevAov aov{};
+    std::vector<void *> aovAllocs;
+    float *fieldPlanes = nullptr;
+    size_t fieldCap = 0;
+    int fieldCount = 0;               // fields the planes were sized for
+    uint32_t nShapes = 0;
+    std::vector<int32_t> bsdfTexture; // mtsg_bsdf::texture of every record (host copy)
+    float *dumpMulti = nullptr;       // mtsg_render_samples_multi
 };
 
 namespace {
@@ -135,6 +147,10 @@ int set_device(mtsg_scene *s) {
 void free_batch(mtsg_scene *s) {
     for (void *p : s->batchAllocs) hipFree(p);
     s->batchAllocs.clear();
+    if (s->fieldPlanes) hipFree(s->fieldPlanes);
+    s->fieldPlanes = nullptr;
+    s->fieldCap = 0;
+    s->fieldCount = 0;
     s->capacity = 0;
     s->lanesAlloc = 0;
 }
@@ -248,7 +264,7 @@ ShadeLaunch shade_args(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B,
     a.bounce = b;
     a.qin = qin;
     a.nIdentity = B.nslots;
-    a.hasAlpha = s->cam.has_alpha;
+    a.hasAlpha = s->cam.has_alpha || s->aovOn;   // multichannel: alpha is always a channel of the block
     a.shadeMin = s->finishShadeMin;
     a.env = s->ds.has_env != 0;
     a.ext = s->extBsdfs;
@@ -342,6 +358,36 @@ DevSampler make_sampler(const mtsg_scene *s, uint32_t spp) {
     return S;
 }
 
+// the SoA field planes of the active child set, one float per path slot and
+// channel; plain renders allocate none (PATH_STATE_BYTES is unchanged)
+int ensure_fields(mtsg_scene *s) {
+    const int nf = s->aov.nf;
+    if (s->fieldPlanes && s->fieldCap >= s->capacity && s->fieldCount >= nf) return MTSG_OK;
+    if (s->fieldPlanes) hipFree(s->fieldPlanes);
+    s->fieldPlanes = nullptr;
+    s->fieldCap = 0;
+    s->fieldCount = 0;
+    if (nf == 0) return MTSG_OK;
+    HIP_TRY(hipMalloc((void **)&s->fieldPlanes, (size_t)s->capacity * nf * 3 * sizeof(float)));
+    s->fieldCap = s->capacity;
+    s->fieldCount = nf;
+    return MTSG_OK;
+}
+FieldsLaunch fields_args(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B, const DevPaths &P, hipStream_t st, float *film,
+                         int blockW, int blockH, int win) {
+    return FieldsLaunch{st, &s->ds, &s->cam, &I, &B, &P, &s->aov, film, blockW, blockH, win};
+}
+void free_aov(mtsg_scene *s) {
+    for (void *p : s->aovAllocs) hipFree(p);
+    s->aovAllocs.clear();
+    if (s->fieldPlanes) hipFree(s->fieldPlanes);
+    s->fieldPlanes = nullptr;
+    s->fieldCap = 0;
+    s->fieldCount = 0;
+    s->aovOn = false;
+    s->aov = DevAov{};
+}
+
 const char *const traversal_error =
     "kd-tree traversal: a ray reached the restart limit without making progress (kernels.h kd_restart)";
 // Mitsuba's Log(EError) of Halton/Hammersley (halton.cpp:343-386) and sobol (sobol.cpp:223-239)
@@ -385,24 +431,34 @@ int validate(const mtsg_render_params *p, const mtsg_scene *s) {
 
 // win = 0: film is the ImageBlock of the whole rectangle + border; win > 0:
 // film holds one win x win window per tile of this call (mtsg_render_device_tiles)
-int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win = 0) {
+int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win = 0, bool multi = false) {
     int rc;
     if ((rc = validate(p, s)) != MTSG_OK) return rc;
+    // a handle with a multichannel child set renders through the *_multi
+    // entries only (3m + 2 floats per texel), a plain handle through the others
+    if (s->aovOn && !multi) {
+        g_err = "the scene's integrator is multichannel: use the _multi render entries (channels are not dropped)";
+        return MTSG_ERR_INVALID;
+    }
+    if (multi && !s->aovOn) { g_err = "no multichannel child set is active (mtsg_scene_set_aov)"; return MTSG_ERR_INVALID; }
+    if (multi && p->integrator != MTSG_INTEGRATOR_PATH) { g_err = "multichannel: only `path` and `field` children"; return MTSG_ERR_INVALID; }
     if ((rc = set_device(s)) != MTSG_OK) return rc;
+    // bytes of state per path: the field planes join it while fields are active
+    const size_t stateBytes = PATH_STATE_BYTES + (multi ? (size_t)s->aov.nf * 3 * sizeof(float) : 0);
     auto t0 = std::chrono::steady_clock::now();
     const bool count = (s->flags & MTSG_FLAG_COUNT) != 0;
     uint32_t maxPaths = s->requestedBatch ? s->requestedBatch : DEFAULT_BATCH_PATHS;
     if (!s->requestedBatch) {
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-            const size_t held = (size_t)s->capacity * s->lanesAlloc * PATH_STATE_BYTES;
+            const size_t held = (size_t)s->capacity * s->lanesAlloc * PATH_STATE_BYTES + (size_t)s->fieldCap * s->fieldCount * 3 * sizeof(float);
             // 3/4 of the free HBM (288 GB on an MI355X: 768M paths, C5's three
             // batches of 713M); the rest stays for the scene and other users
-            const size_t fit = (size_t)((freeB + held) * 0.75 / PATH_STATE_BYTES);
+            const size_t fit = (size_t)((freeB + held) * 0.75 / stateBytes);
             maxPaths = (uint32_t)std::max<size_t>(TILE * TILE, std::min<size_t>(maxPaths, fit));
         }
     }
-    if (s->dumpL && (uint64_t)p->tile_w * p->tile_h * p->spp > maxPaths) { g_err = "render_samples: tile does not fit one batch"; return MTSG_ERR_INVALID; }
+    if ((s->dumpL || s->dumpMulti) && (uint64_t)p->tile_w * p->tile_h * p->spp > maxPaths) { g_err = "render_samples: tile does not fit one batch"; return MTSG_ERR_INVALID; }
     const uint32_t tilesX = (uint32_t)(p->tile_w + TILE - 1) / TILE, tilesY = (uint32_t)(p->tile_h + TILE - 1) / TILE;
     const uint32_t allTiles = tilesX * tilesY;
     const uint32_t tstride = p->tile_stride > 1 ? (uint32_t)p->tile_stride : 1u;
@@ -417,7 +473,8 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
     // Lanes: independent batches on their own streams, issued bounce by bounce
     // in lock step, so one lane's launch tail (its slowest rays) overlaps the
     // other lane's launch.  The debug and counting modes use one lane.
-    const uint32_t nl = (s->dumpL || count || ntiles < 2) ? 1u : (uint32_t)s->lanes;
+    // (multichannel too: one set of field planes)
+    const uint32_t nl = (s->dumpL || s->dumpMulti || count || ntiles < 2 || multi) ? 1u : (uint32_t)s->lanes;
     const uint32_t lanePaths = std::max<uint32_t>(TILE * TILE, maxPaths / nl);
     const uint32_t sppPerBatch = std::max(1u, std::min(p->spp, lanePaths / (TILE * TILE)));
     // equal-sized batches, a multiple of the lane count: a nearly empty last
@@ -428,6 +485,12 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
     nTileBatches = std::min(ntiles ? ntiles : 1u, (nTileBatches + nl - 1) / nl * nl);
     const uint32_t tilesPerBatch = std::max(1u, (ntiles + nTileBatches - 1) / nTileBatches);
     if ((rc = ensure_batch(s, tilesPerBatch * sppPerBatch * TILE * TILE, (int)nl)) != MTSG_OK) return rc;
+    const bool fieldsOnly = multi && s->aov.pathChild < 0;
+    if (multi) {
+        if ((rc = ensure_fields(s)) != MTSG_OK) return rc;
+        s->aov.planes = s->fieldPlanes;
+        s->aov.cap = s->fieldCap;
+    }
     const int blockW = p->tile_w + 2 * s->cam.border, blockH = p->tile_h + 2 * s->cam.border;
     DevIntegrator I{p->max_depth, p->rr_depth, p->strict_normals, p->hide_emitters, p->spp, p->seed, (uint32_t)s->cam.film_w,
                     make_sampler(s, p->spp)};
@@ -557,6 +620,21 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
                     PT.order = P.orderBuf;
                 }
                 timed_launch(s, K_CLOSEST, st, [&]() { launch_trace(s, count, PT, qin, b == 0 ? -1 : ((b - 1) & 1), L.B.nslots, st); });
+                if (multi && b == 0) {
+                    // the bounce-0 hits are final (the tie retrace is part of the trace
+                    // launch) and the work list is the identity: the field children
+                    if (s->aov.nf || fieldsOnly) launch_fields(fields_args(s, I, L.B, P, st, film, blockW, blockH, win));
+                    if (fieldsOnly) {
+                        // no `path` child: no shading, no further bounce; the counters'
+                        // copy carries the traversal's error word
+                        HIP_TRY(hipMemcpyAsync(hostCnt(l, 0), P.cnt, (CNT_S1 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                        HIP_TRY(hipEventRecord(L.cntEv[0], st));
+                        L.last = 0;
+                        L.open = false;
+                        L.finished = true;
+                        continue;
+                    }
+                }
                 if (useFinish && b >= 1) {
                     // the count of this bounce's paths is known once bounce b-1 is
                     // done (the GPU meanwhile runs this bounce's trace): few left ->
@@ -613,7 +691,8 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
                 HIP_TRY(hipMemcpyAsync(hostCnt(l, L.last) + CNT_ERR, P.cnt + CNT_ERR, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipEventRecord(L.cntEv[L.last & 1], st));
             }
-            timed_launch(s, K_SPLAT, st, [&]() {
+            if (multi) timed_launch(s, K_SPLAT, st, [&]() { launch_splat_multi(fields_args(s, I, B, P, st, film, blockW, blockH, win)); });
+            else timed_launch(s, K_SPLAT, st, [&]() {
                 dim3 g(B.ntiles, (B.ns + SPLAT_CHUNK - 1) / SPLAT_CHUNK);
                 const int K = 2 * s->cam.border + 1;
                 if (K == 5 && !s->cam.has_alpha) hipLaunchKernelGGL((k_splat<5, 4>), g, dim3(BLOCK), 0, st, s->cam, I, B, P, film, blockW, blockH, win);
@@ -629,7 +708,17 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
             LaneRun &L = lr[l];
             if (L.last < 0) continue;
             HIP_TRY(hipEventSynchronize(L.cntEv[L.last & 1]));
-            account(l, L.last);
+            if (fieldsOnly) {
+                // one closest launch per batch, one camera ray per sample inside the rectangle
+                s->stats.launches_trace_closest++;
+                for (int tl = 0; tl < L.B.ntiles; ++tl) {
+                    int tx, ty;
+                    tile_of_key(hostKey(L.B.tile0 + tl), L.B.tiles_x, tx, ty, L.B.skew);
+                    s->stats.rays_closest += (uint64_t)std::min(TILE, p->tile_w - tx * TILE) * std::min(TILE, p->tile_h - ty * TILE) * L.B.ns;
+                }
+            } else {
+                account(l, L.last);
+            }
             // the error word is sticky within the batch: the last copy holds it
             const uint32_t err = hostCnt(l, L.last)[CNT_ERR];
             if (err & CNT_ERR_TRAVERSAL) {
@@ -655,6 +744,35 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
                     s->tileFn(s->tileUser, key, p->tile_x + x, p->tile_y + y, std::min(TILE, p->tile_w - x),
                               std::min(TILE, p->tile_h - y));
                 }
+            }
+        }
+        if (s->dumpMulti) {
+            // debug: the batch's per-slot children (single batch, one lane): the
+            // `path` child and alpha from L, the fields from their planes
+            const DevBatch &B = lr[0].B;
+            const DevAov &A = s->aov;
+            std::vector<float4> L(B.nslots);
+            std::vector<float> F((size_t)3 * A.nf * B.nslots);
+            HIP_TRY(hipMemcpyAsync(L.data(), s->LP[0].L, B.nslots * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
+            for (int k = 0; k < 3 * A.nf; ++k)
+                HIP_TRY(hipMemcpyAsync(F.data() + (size_t)k * B.nslots, A.planes + (size_t)k * A.cap, B.nslots * sizeof(float),
+                                       hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            const size_t per = (size_t)3 * A.m + 1;
+            for (uint32_t slot = 0; slot < B.nslots; ++slot) {
+                const uint32_t pix = slot & (TILE * TILE - 1), rest = slot >> 8;
+                const uint32_t sl = rest % B.ns, tl = rest / B.ns;
+                int tx, ty;
+                tile_of_key(hostKey(B.tile0 + (int)tl), B.tiles_x, tx, ty, B.skew);
+                int lx, ly;
+                tile_pix(pix, lx, ly);
+                const int x = tx * TILE + lx, y = ty * TILE + ly;
+                if (x >= p->tile_w || y >= p->tile_h) continue;
+                float *o = s->dumpMulti + (((size_t)y * p->tile_w + x) * p->spp + B.s0 + sl) * per;
+                if (A.pathChild >= 0) { o[3 * A.pathChild] = L[slot].x; o[3 * A.pathChild + 1] = L[slot].y; o[3 * A.pathChild + 2] = L[slot].z; }
+                for (int f = 0; f < A.nf; ++f)
+                    for (int c = 0; c < 3; ++c) o[3 * A.child[f] + c] = F[(size_t)(3 * f + c) * B.nslots + slot];
+                o[3 * A.m] = L[slot].w;
             }
         }
         if (s->dumpL) {
@@ -1161,6 +1279,16 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
             if (!ok) { g_err = "texture " + std::to_string(i) + ": malformed MIP map"; return fail(MTSG_ERR_INVALID); }
             texDiffs |= M.filter == MTSG_MIP_TRILINEAR || M.filter == MTSG_MIP_EWA;
         }
+        mtsg_texture *dtex; float *dtt;
+        if ((rc = up(d->textures, d->n_textures, &dtex)) || (rc = up(d->tex_texels, d->n_tex_texels, &dtt)))
+            return fail(rc);
+        ds.textures = dtex; ds.tex_texels = dtt;
+        s->nTextures = d->n_textures;
+        s->extBsdfs = true;   // texture lookups live in the extended shade kernel
+    }
+    // the per-triangle texture records: with textures, or for the `uv` field of
+    // a multichannel scene without any (the builder fills tri_uv for it)
+    if (d->tri_uv && d->tri_dpdv) {
         std::vector<float4> tt((size_t)3 * std::max(1u, d->n_triangles), make_float4(0, 0, 0, 0));
         for (uint32_t t = 0; t < d->n_triangles; ++t) {
             const float *uv = d->tri_uv + 6 * (size_t)t, *dv = d->tri_dpdv + 3 * (size_t)t;
@@ -1168,14 +1296,13 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
             tt[3 * t + 1] = make_float4(uv[4], uv[5], dv[0], dv[1]);
             tt[3 * t + 2] = make_float4(dv[2], 0.f, 0.f, 0.f);
         }
-        mtsg_texture *dtex; float *dtt; float4 *dttex;
-        if ((rc = up(d->textures, d->n_textures, &dtex)) || (rc = up(d->tex_texels, d->n_tex_texels, &dtt)) ||
-            (rc = up(tt.data(), tt.size(), &dttex)))
-            return fail(rc);
-        ds.textures = dtex; ds.tex_texels = dtt; ds.ttex = dttex;
-        s->nTextures = d->n_textures;
-        s->extBsdfs = true;   // texture lookups live in the extended shade kernel
+        float4 *dttex;
+        if ((rc = up(tt.data(), tt.size(), &dttex))) return fail(rc);
+        ds.ttex = dttex;
     }
+    s->nShapes = d->n_shapes;
+    s->bsdfTexture.resize(d->n_bsdfs);
+    for (uint32_t i = 0; i < d->n_bsdfs; ++i) s->bsdfTexture[i] = d->bsdfs[i].texture;
     s->texDiffs = texDiffs;
     s->hasEnvmap = d->has_envmap != 0;
     // myPath2_OM occupancy maps (om.cpp)
@@ -1459,6 +1586,119 @@ int mtsg_device_to_host(mtsg_scene *s, void *dst, const void *src, size_t bytes)
     if ((rc = set_device(s)) != MTSG_OK) return rc;
     HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return MTSG_OK;
+}
+
+int mtsg_scene_set_aov(mtsg_scene *s, const mtsg_aov_desc *d) {
+    if (!s) { g_err = "null scene"; return MTSG_ERR_INVALID; }
+    int rc;
+    if ((rc = set_device(s)) != MTSG_OK) return rc;
+    if (!d) { free_aov(s); return MTSG_OK; }
+    if (d->n_children < 1 || d->n_children > MTSG_MAX_SUBINTEGRATORS) {
+        g_err = "multichannel: 1 to " + std::to_string(MTSG_MAX_SUBINTEGRATORS) + " child integrators";
+        return MTSG_ERR_INVALID;
+    }
+    if (d->n_bsdfs != s->ds.n_bsdfs || d->n_shapes != s->nShapes || (d->n_bsdfs && !d->bsdfs) || (d->n_shapes && !d->shapes) ||
+        (d->n_elems && !d->elem_starts)) {
+        g_err = "multichannel: the descriptor's BSDF / shape tables do not match the scene";
+        return MTSG_ERR_INVALID;
+    }
+    DevAov A{};
+    A.m = (int)d->n_children;
+    A.pathChild = -1;
+    bool needUv = false;
+    for (int k = 0; k < A.m; ++k) {
+        const mtsg_aov_child &c = d->children[k];
+        if (c.kind == MTSG_AOV_PATH) {
+            if (A.pathChild >= 0) { g_err = "multichannel: at most one `path` child"; return MTSG_ERR_INVALID; }
+            A.pathChild = k;
+            continue;
+        }
+        if (c.kind < MTSG_FIELD_POSITION || c.kind > MTSG_FIELD_PRIM_INDEX) { g_err = "multichannel: unknown child kind"; return MTSG_ERR_INVALID; }
+        A.kind[A.nf] = c.kind;
+        A.child[A.nf] = k;
+        for (int j = 0; j < 3; ++j) A.undef[A.nf][j] = c.undefined[j];
+        needUv |= c.kind == MTSG_FIELD_UV;
+        ++A.nf;
+    }
+    for (uint32_t i = 0; i < d->n_bsdfs; ++i)
+        if (d->bsdfs[i].textured) {
+            if (!s->bsdfTexture[i]) { g_err = "multichannel: a textured albedo record on a BSDF without a texture"; return MTSG_ERR_INVALID; }
+            needUv = true;
+        }
+    if (needUv && s->ds.n_tri && !s->ds.ttex) {
+        g_err = "multichannel: the `uv` field and textured albedos need the scene's tri_uv / tri_dpdv";
+        return MTSG_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < d->n_shapes; ++i) {
+        const mtsg_aov_shape &sh = d->shapes[i];
+        if (sh.elem_count < 1 || (uint64_t)sh.elem_offset + sh.elem_count > d->n_elems) {
+            g_err = "multichannel: shape " + std::to_string(i) + " has an invalid element range";
+            return MTSG_ERR_INVALID;
+        }
+    }
+    memcpy(A.w2c, d->world_to_camera, sizeof(A.w2c));
+    free_aov(s);
+    mtsg_aov_bsdf *db = nullptr;
+    mtsg_aov_shape *dsh = nullptr;
+    uint32_t *de = nullptr;
+    auto up = [&](auto *src, size_t n, auto **dst) {
+        int r = upload(src, n, dst);
+        if (*dst) s->aovAllocs.push_back((void *)*dst);
+        return r;
+    };
+    if ((rc = up(d->bsdfs, d->n_bsdfs, &db)) || (rc = up(d->shapes, d->n_shapes, &dsh)) || (rc = up(d->elem_starts, d->n_elems, &de))) {
+        free_aov(s);
+        return rc;
+    }
+    A.bsdfs = db;
+    A.shapes = dsh;
+    A.elems = de;
+    s->aov = A;
+    s->aovOn = true;
+    return MTSG_OK;
+}
+
+int mtsg_render_device_multi(mtsg_scene *s, const mtsg_render_params *p, float *film) {
+    if (!s || !film) { g_err = "null argument"; return MTSG_ERR_INVALID; }
+    return render_impl(s, p, film, 0, true);
+}
+
+int mtsg_render_device_tiles_multi(mtsg_scene *s, const mtsg_render_params *p, float *windows) {
+    if (!s || !windows) { g_err = "null argument"; return MTSG_ERR_INVALID; }
+    return render_impl(s, p, windows, TILE + 2 * s->cam.border, true);
+}
+
+int mtsg_render_multi(mtsg_scene *s, const mtsg_render_params *p, float *out) {
+    if (!s || !out) { g_err = "null argument"; return MTSG_ERR_INVALID; }
+    if (!s->aovOn) { g_err = "no multichannel child set is active (mtsg_scene_set_aov)"; return MTSG_ERR_INVALID; }
+    int rc;
+    if ((rc = validate(p, s)) != MTSG_OK) return rc;
+    if ((rc = set_device(s)) != MTSG_OK) return rc;
+    const size_t bytes =
+        (size_t)(p->tile_w + 2 * s->cam.border) * (p->tile_h + 2 * s->cam.border) * (3 * (size_t)s->aov.m + 2) * sizeof(float);
+    float *film = nullptr;
+    HIP_TRY(hipMalloc((void **)&film, bytes));
+    hipError_t e = hipMemsetAsync(film, 0, bytes, s->stream);
+    if (e != hipSuccess) { hipFree(film); g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
+    rc = render_impl(s, p, film, 0, true);
+    if (rc == MTSG_OK) {
+        e = hipMemcpy(out, film, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { g_err = hipGetErrorString(e); rc = MTSG_ERR_DEVICE; }
+    }
+    hipFree(film);
+    return rc;
+}
+
+int mtsg_render_samples_multi(mtsg_scene *s, const mtsg_render_params *p, float *out) {
+    if (!s || !out || !p) { g_err = "null argument"; return MTSG_ERR_INVALID; }
+    if (!s->aovOn) { g_err = "no multichannel child set is active (mtsg_scene_set_aov)"; return MTSG_ERR_INVALID; }
+    int rcv;
+    if ((rcv = validate(p, s)) != MTSG_OK) return rcv;
+    s->dumpMulti = out;
+    std::vector<float> block((size_t)(p->tile_w + 2 * s->cam.border) * (p->tile_h + 2 * s->cam.border) * (3 * (size_t)s->aov.m + 2));
+    const int rc = mtsg_render_multi(s, p, block.data());
+    s->dumpMulti = nullptr;
+    return rc;
 }
 
 int mtsg_render_device(mtsg_scene *s, const mtsg_render_params *p, float *film) {
@@ -1783,6 +2023,7 @@ void mtsg_scene_destroy(mtsg_scene *s) {
         if (s->lstream[l]) hipStreamDestroy(s->lstream[l]);
     if (s->stream) hipStreamDestroy(s->stream);
     if (s->tileKeysDev) hipFree(s->tileKeysDev);
+    free_aov(s);
     delete s;
 }
 

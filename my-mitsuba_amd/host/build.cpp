@@ -189,7 +189,10 @@ void Scene::setTree(const mtsg_kdnode *nodes, uint32_t nNodes, const uint32_t *i
 void Scene::finalize() {
     // ---------------- geometry ----------------
     vtxPos.clear(); vtxNrm.clear(); triIdx.clear(); triDpdu.clear(); triUv.clear(); triDpdv.clear();
-    const bool texData = !textures.empty();
+    // tri_uv / tri_dpdv: for texture lookups, and for the `uv` field of a
+    // multichannel integrator even without textures
+    bool texData = !textures.empty();
+    for (const auto &c : integrator.children) texData |= c.kind == MTSG_FIELD_UV;
     shapeDesc.clear(); rectDesc.clear();
     std::vector<uint32_t> meshTriBegin(meshes.size());
     for (size_t si = 0; si < shapes.size(); ++si) {

@@ -560,6 +560,7 @@ int SceneBuilder::group(const std::string &id) {
     if (id.empty()) throw err("shapegroup needs an id");
     ShapeGroup g;
     g.id = id;
+    ++nextSceneIndex;   // the ShapeGroup itself is an entry of Scene::m_shapes
     if (scene.twoLevel) {
         // ShapeGroup::addChild / configure (shapegroup.cpp:94-138): the
         // group's shapes get their own kd-tree in group space
@@ -581,7 +582,7 @@ void SceneBuilder::addRect(Rect r, int group) {
     if (group < 0) {
         scene.rects.push_back(r);
         const int si = (int)scene.shapes.size();
-        scene.shapes.push_back({MTSG_SHAPE_RECT, (int)scene.rects.size() - 1});
+        scene.shapes.push_back({MTSG_SHAPE_RECT, (int)scene.rects.size() - 1, curSceneIndex});
         if (r.emitter >= 0) scene.emitters[r.emitter].shape = si;
         return;
     }
@@ -599,7 +600,7 @@ void SceneBuilder::addMesh(Mesh &&m, int group) {
     if (group < 0) {
         scene.meshes.push_back(std::move(m));
         const int si = (int)scene.shapes.size();
-        scene.shapes.push_back({MTSG_SHAPE_MESH, (int)scene.meshes.size() - 1});
+        scene.shapes.push_back({MTSG_SHAPE_MESH, (int)scene.meshes.size() - 1, curSceneIndex});
         if (scene.meshes.back().emitter >= 0) scene.emitters[scene.meshes.back().emitter].shape = si;
         return;
     }
@@ -629,7 +630,16 @@ void SceneBuilder::mesh(Mesh &&m, const Transform *toWorld, bool flip, int bsdf,
     computeNormals(m, flip);
     m.bsdf = bsdf;
     m.emitter = emitter;
+    // a top-level shape takes the next Scene::m_shapes position(s), one per
+    // element of a compound shape (Scene::addShape, scene.cpp:608-647); the
+    // shapes of a shapegroup are not in the list
+    curSceneIndex = -1;
+    if (group < 0) {
+        curSceneIndex = nextSceneIndex;
+        nextSceneIndex += std::max<int>(1, (int)m.elemStart.size());
+    }
     addMesh(std::move(m), group);
+    curSceneIndex = -1;
 }
 
 void SceneBuilder::shape(const std::string &type_, const Properties &props, int bsdf, int emitter, int group, int line) {
@@ -648,14 +658,16 @@ void SceneBuilder::shape(const std::string &type_, const Properties &props, int 
         if (flip) r.toWorld = r.toWorld * Transform::scale(V3(1, 1, -1));
         r.bsdf = bsdf;
         r.emitter = emitter;
+        curSceneIndex = group < 0 ? nextSceneIndex++ : -1;
         addRect(r, group);
+        curSceneIndex = -1;
         return;
     }
     Mesh m;
     if (type == "ply") {
         loadPLY(resolve(props.getString("filename", "")), m);
     } else if (type == "obj") {
-        loadOBJ(resolve(props.getString("filename", "")), m, props.getBool("flipTexCoords", true));
+        loadOBJ(resolve(props.getString("filename", "")), m, props.getBool("flipTexCoords", true), props.getBool("collapse", false));
     } else if (type == "cube") {
         buildCube(m);
     } else if (type == "serialized") {
@@ -680,6 +692,10 @@ void SceneBuilder::shape(const std::string &type_, const Properties &props, int 
 
 void SceneBuilder::instance(int group, const Transform &toWorld) {
     const ShapeGroup &g = groupAt(group);
+    // the Instance is an entry of Scene::m_shapes; a hit inside it reports the
+    // group's mesh, which is not (curSceneIndex stays -1 for the flattened copies)
+    const int instIndex = nextSceneIndex++;
+    curSceneIndex = -1;
     if (scene.twoLevel) {
         // Instance (instance.cpp:57-130): a top-level primitive that
         // transforms rays into the group's space
@@ -687,7 +703,7 @@ void SceneBuilder::instance(int group, const Transform &toWorld) {
         idf.group = g.index;
         idf.toWorld = toWorld;
         scene.instances.push_back(idf);
-        scene.shapes.push_back({MTSG_SHAPE_INSTANCE, (int)scene.instances.size() - 1});
+        scene.shapes.push_back({MTSG_SHAPE_INSTANCE, (int)scene.instances.size() - 1, instIndex});
         return;
     }
     // flattened: the group's shapes in world space join the scene
@@ -753,7 +769,9 @@ void SceneBuilder::integrator(const std::string &type, const Properties &props, 
         return;
     }
     const std::string t = lower(type);
-    if (t != "path") throw err(at(line) + "integrator \"" + t + "\" is outside this build's scope (only 'path' and 'myPath2_OM')");
+    if (t == "multichannel") { multichannel(props, line); return; }
+    if (t != "path")
+        throw err(at(line) + "integrator \"" + t + "\" is outside this build's scope (only 'path', 'multichannel' and 'myPath2_OM')");
     // MonteCarloIntegrator(props) (integrator.cpp:199-234)
     ip = IntegratorProps();
     ip.type = t;
@@ -763,6 +781,54 @@ void SceneBuilder::integrator(const std::string &type, const Properties &props, 
     ip.hideEmitters = props.getBool("hideEmitters", false);
     if (ip.rrDepth <= 0) throw err("'rrDepth' must be set to a value greater than zero!");
     if (ip.maxDepth <= 0 && ip.maxDepth != -1) throw err("'maxDepth' must be set to -1 (infinite) or a value greater than zero!");
+}
+
+// A child of `multichannel` (MultiChannelIntegrator::addChild,
+// multichannel.cpp:219-231, takes any SamplingIntegrator; this build `path`
+// and `field`, field.cpp:69-110)
+int SceneBuilder::integratorChild(const std::string &type, const Properties &props, int line) {
+    const std::string t = type == "myPath2_OM" ? type : lower(type);
+    IntegratorProps::Child c{MTSG_AOV_PATH, V3(0.0f)};
+    if (t == "path") {
+        if (havePendingPath) throw err(at(line) + "multichannel: at most one 'path' child is supported by this build");
+        const IntegratorProps keep = scene.integrator;
+        integrator("path", props, line);   // MonteCarloIntegrator's properties and checks
+        pendingPath = scene.integrator;
+        scene.integrator = keep;
+        havePendingPath = true;
+    } else if (t == "field") {
+        static const std::map<std::string, int> fields = {
+            {"position", MTSG_FIELD_POSITION}, {"relPosition", MTSG_FIELD_REL_POSITION}, {"distance", MTSG_FIELD_DISTANCE},
+            {"geoNormal", MTSG_FIELD_GEO_NORMAL}, {"shNormal", MTSG_FIELD_SH_NORMAL}, {"uv", MTSG_FIELD_UV},
+            {"albedo", MTSG_FIELD_ALBEDO}, {"shapeIndex", MTSG_FIELD_SHAPE_INDEX}, {"primIndex", MTSG_FIELD_PRIM_INDEX}};
+        if (!props.strings.count("field")) throw err(at(line) + "Property \"field\" has not been specified!");
+        const auto it = fields.find(props.strings.at("field"));
+        if (it == fields.end())
+            throw err(at(line) + "Invalid 'field' parameter. Must be one of 'position', 'relPosition', 'distance', 'geoNormal', "
+                                 "'shNormal', 'primIndex', 'shapeIndex', or 'uv'!");
+        c.kind = it->second;
+        // a float or a spectrum (field.cpp:96-104)
+        c.undefined = props.getSpectrum("undefined", V3(0.0f));
+    } else if (t == "multichannel") {
+        throw err(at(line) + "multichannel: a nested 'multichannel' integrator is not supported");
+    } else {
+        throw err(at(line) + "multichannel: child integrator \"" + t + "\" is outside this build's scope (only 'path' and 'field')");
+    }
+    if (pendingChildren.size() >= MTSG_MAX_SUBINTEGRATORS)
+        throw err(at(line) + "multichannel: more than " + std::to_string(MTSG_MAX_SUBINTEGRATORS) + " child integrators");
+    pendingChildren.push_back(c);
+    return (int)pendingChildren.size() - 1;
+}
+
+void SceneBuilder::multichannel(const Properties &, int line) {
+    if (pendingChildren.empty()) throw err(at(line) + "multichannel: at least one child integrator is required");
+    IntegratorProps ip = havePendingPath ? pendingPath : IntegratorProps();
+    ip.type = "path";   // the render parameters of its `path` child (the defaults without one)
+    ip.multichannel = true;
+    ip.children = pendingChildren;
+    scene.integrator = ip;
+    pendingChildren.clear();
+    havePendingPath = false;
 }
 
 void SceneBuilder::sensor(const std::string &type_, const Properties &props, int line) {
@@ -826,7 +892,55 @@ void SceneBuilder::film(const std::string &type_, const Properties &props) {
     f.cropW = (int)props.getInt("cropWidth", f.width);
     f.cropH = (int)props.getInt("cropHeight", f.height);
     f.pixelFormat = lower(props.getString("pixelFormat", "rgb"));
-    f.hasAlpha = f.pixelFormat.find('a') != std::string::npos;
+    // hdrfilm.cpp:216-243: comma / space separated lists
+    auto tokens = [](const std::string &v) {
+        std::vector<std::string> out;
+        std::string cur;
+        for (char c : v) {
+            if (c == ',' || c == ' ') { if (!cur.empty()) out.push_back(cur); cur.clear(); }
+            else cur += c;
+        }
+        if (!cur.empty()) out.push_back(cur);
+        return out;
+    };
+    f.pixelFormats = tokens(f.pixelFormat);
+    f.channelNames = tokens(props.getString("channelNames", ""));
+    if (f.pixelFormats.empty()) throw err("At least one pixel format must be specified!");
+    if ((f.pixelFormats.size() != 1 && f.channelNames.size() != f.pixelFormats.size()) ||
+        (f.pixelFormats.size() == 1 && f.channelNames.size() > 1))
+        throw err("Number of channel names must match the number of specified pixel formats!");
+    if (f.pixelFormats.size() != 1 && props.strings.count("fileFormat") && lower(props.strings.at("fileFormat")) != "openexr")
+        throw err("General multi-channel output is only supported when writing OpenEXR files!");
+    {
+        std::vector<std::string> ch;
+        std::vector<int> ids;
+        if (f.pixelFormats.size() > 1 || !f.channelNames.empty()) filmChannels(f.pixelFormats, f.channelNames, ch, ids);   // validates the entries
+    }
+    // a single entry keeps this build's reading of it (an 'a' = an alpha channel)
+    f.hasAlpha = f.pixelFormats.size() == 1 && f.pixelFormat.find('a') != std::string::npos;
+}
+
+void filmChannels(const std::vector<std::string> &formats, const std::vector<std::string> &names, std::vector<std::string> &channels,
+                  std::vector<int> &formatIds) {
+    channels.clear();
+    formatIds.clear();
+    for (size_t i = 0; i < formats.size(); ++i) {
+        const std::string pf = lower(formats[i]);
+        const std::string name = i < names.size() ? names[i] + "." : "";
+        int id;
+        std::vector<const char *> ch;
+        if (pf == "luminance") { id = MTSH_FORMAT_LUMINANCE; ch = {"Y"}; }
+        else if (pf == "luminancealpha") { id = MTSH_FORMAT_LUMINANCE_ALPHA; ch = {"Y", "A"}; }
+        else if (pf == "rgb") { id = MTSH_FORMAT_RGB; ch = {"R", "G", "B"}; }
+        else if (pf == "rgba") { id = MTSH_FORMAT_RGBA; ch = {"R", "G", "B", "A"}; }
+        else if (pf == "xyz") { id = MTSH_FORMAT_XYZ; ch = {"X", "Y", "Z"}; }
+        else if (pf == "xyza") { id = MTSH_FORMAT_XYZA; ch = {"X", "Y", "Z", "A"}; }
+        else
+            throw err("The \"pixelFormat\" parameter must either be equal to \"luminance\", \"luminanceAlpha\", \"rgb\", "
+                      "\"rgba\", \"xyz\" or \"xyza\" (spectral formats are outside this RGB build)!");
+        formatIds.push_back(id);
+        for (const char *c : ch) channels.push_back(name + c);
+    }
 }
 
 void SceneBuilder::rfilter(const std::string &type_, const Properties &fp) {
@@ -889,7 +1003,71 @@ void SceneBuilder::finish(const mtsh_scene_overrides *ov) {
             ip.hideEmitters = ov->hide_emitters != 0;
         }
     }
+    if (!pendingChildren.empty()) throw err("multichannel: child integrators were added but the parent was not set");
+    if (scene.integrator.multichannel) {
+        if (scene.film.pixelFormats.size() != scene.integrator.children.size())
+            throw err("multichannel: the film's pixelFormat lists " + std::to_string(scene.film.pixelFormats.size()) +
+                      " entries for " + std::to_string(scene.integrator.children.size()) + " child integrators "
+                      "(Number of pixel formats must match the number of sub-integrators!)");
+    } else if (scene.film.pixelFormats.size() != 1) {
+        throw err("the film's pixelFormat lists " + std::to_string(scene.film.pixelFormats.size()) +
+                  " entries, but the integrator produces one channel set (use 'multichannel')");
+    }
     scene.finalize();
+    scene.buildAov();
+}
+
+// The multichannel descriptor beside the scene descriptor (mtsg.h
+// mtsg_aov_desc): children, getDiffuseReflectance per BSDF record, the
+// Scene::m_shapes positions, and the sensor's world-to-camera transform
+void Scene::buildAov() {
+    aovBsdfs.clear(); aovShapes.clear(); aovElems.clear();
+    memset(&aovDesc, 0, sizeof(aovDesc));
+    if (!integrator.multichannel) return;
+    mtsg_aov_desc &a = aovDesc;
+    a.n_children = (uint32_t)integrator.children.size();
+    for (size_t k = 0; k < integrator.children.size(); ++k) {
+        a.children[k].kind = integrator.children[k].kind;
+        for (int j = 0; j < 3; ++j) a.children[k].undefined[j] = integrator.children[k].undefined[j];
+    }
+    // field.cpp:137-142: sensor->getWorldTransform()->eval(t).inverse(), the
+    // inverse the Transform already holds
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) a.world_to_camera[4 * r + c] = sensor.toWorld.inv[r][c];
+    for (const mtsg_bsdf &b : bsdfDesc) {
+        mtsg_aov_bsdf ab{};
+        V3 f(0.0f);   // conductors, dielectrics: BSDF::getDiffuseReflectance = eval(EDiffuseReflection) * pi = 0 (bsdf.cpp:82-86)
+        float scale = 0.0f;
+        bool diffuse = true;
+        if (b.type == MTSG_BSDF_DIFFUSE) scale = 1.0f;   // diffuse.cpp:106-108
+        else if (b.type == MTSG_BSDF_PLASTIC) scale = 1 - fresnelDiffuseReflectance(b.ior_eta);   // plastic.cpp:195,219-221
+        else if (b.type == MTSG_BSDF_ROUGHPLASTIC)   // roughplastic.cpp:309-320: Ftr = external evalDiffuse(alpha)
+            scale = roughDiffuseTransmittance(b.distribution, b.alpha_u, b.ior_eta);
+        else diffuse = false;
+        if (diffuse) {
+            ab.textured = b.texture ? 1 : 0;
+            f = b.texture ? V3(scale) : (b.type == MTSG_BSDF_DIFFUSE ? V3(b.reflectance[0], b.reflectance[1], b.reflectance[2])
+                                                                    : V3(b.reflectance[0], b.reflectance[1], b.reflectance[2]) * scale);
+        }
+        for (int j = 0; j < 3; ++j) ab.factor[j] = f[j];
+        aovBsdfs.push_back(ab);
+    }
+    for (size_t si = 0; si < shapes.size(); ++si) {
+        mtsg_aov_shape sh{};
+        sh.scene_index = shapes[si].sceneIndex;
+        sh.elem_offset = (uint32_t)aovElems.size();
+        const std::vector<uint32_t> *es = shapes[si].type == MTSG_SHAPE_MESH ? &meshes[shapes[si].index].elemStart : nullptr;
+        if (es && !es->empty()) aovElems.insert(aovElems.end(), es->begin(), es->end());
+        else aovElems.push_back(0u);
+        sh.elem_count = (uint32_t)aovElems.size() - sh.elem_offset;
+        aovShapes.push_back(sh);
+    }
+    a.n_bsdfs = (uint32_t)aovBsdfs.size();
+    a.bsdfs = aovBsdfs.data();
+    a.n_shapes = (uint32_t)aovShapes.size();
+    a.shapes = aovShapes.data();
+    a.n_elems = (uint32_t)aovElems.size();
+    a.elem_starts = aovElems.data();
 }
 
 }  // namespace mtsh

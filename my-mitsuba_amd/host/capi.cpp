@@ -248,6 +248,17 @@ int32_t mtsh_scene_set_integrator(mtsh_builder *b, const char *plugin, const mts
     });
 }
 
+int32_t mtsh_scene_add_integrator_child(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n) {
+    return guarded(b, [&] { return (int32_t)b->b->integratorChild(plugin ? plugin : "", toProps(props, n)); });
+}
+
+int32_t mtsh_scene_set_multichannel(mtsh_builder *b, const mtsh_prop *props, int32_t n) {
+    return guarded(b, [&] {
+        b->b->multichannel(toProps(props, n));
+        return 0;
+    });
+}
+
 mtsh_scene *mtsh_scene_finish(mtsh_builder *b, const mtsh_scene_overrides *overrides) {
     if (!b) { g_err = "invalid builder"; return nullptr; }
     std::unique_ptr<mtsh_builder> own(b);
@@ -269,6 +280,42 @@ int32_t mtsh_scene_digest(const mtsh_scene *s, mtsh_digest_entry *out, int32_t c
     const auto d = mtsh::sceneDigest(s->scene->desc);
     for (int32_t i = 0; out && i < (int32_t)d.size() && i < capacity; ++i) out[i] = d[i];
     return (int32_t)d.size();
+}
+
+const mtsg_aov_desc *mtsh_scene_aov(const mtsh_scene *s) {
+    return s && s->scene->integrator.multichannel ? &s->scene->aovDesc : nullptr;
+}
+
+int mtsh_scene_film_formats(const mtsh_scene *s, int32_t *formats, int capacity) {
+    try {
+        std::vector<std::string> ch;
+        std::vector<int> ids;
+        mtsh::filmChannels(s->scene->film.pixelFormats, s->scene->film.channelNames, ch, ids);
+        for (int i = 0; formats && i < (int)ids.size() && i < capacity; ++i) formats[i] = ids[i];
+        return (int)ids.size();
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
+int mtsh_scene_film_channels(const mtsh_scene *s, char *buf, size_t buf_size) {
+    try {
+        std::vector<std::string> ch;
+        std::vector<int> ids;
+        mtsh::filmChannels(s->scene->film.pixelFormats, s->scene->film.channelNames, ch, ids);
+        size_t need = 0;
+        for (auto &c : ch) need += c.size() + 1;
+        if (buf) {
+            if (buf_size < need) { g_err = "mtsh_scene_film_channels: buffer too small"; return -2; }
+            char *o = buf;
+            for (auto &c : ch) { memcpy(o, c.c_str(), c.size() + 1); o += c.size() + 1; }
+        }
+        return (int)ch.size();
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
 }
 
 void mtsh_scene_render_params(const mtsh_scene *s, mtsg_render_params *p) {
@@ -385,6 +432,62 @@ void mtsh_develop(const float *rgbaw, int w, int h, float *rgb) {
         float wt = rgbaw[5 * i + 4];
         float inv = wt != 0 ? 1.0f / wt : 0.0f;
         for (int k = 0; k < 3; ++k) rgb[3 * i + k] = rgbaw[5 * i + k] * inv;
+    }
+}
+
+int mtsh_develop_multi(const float *block, int w, int h, const int32_t *formats, int n, float *out) {
+    if (!block || !formats || !out || w <= 0 || h <= 0 || n < 1 || n > MTSG_MAX_SUBINTEGRATORS) {
+        g_err = "mtsh_develop_multi: invalid arguments";
+        return -1;
+    }
+    int per = 0;
+    for (int i = 0; i < n; ++i) {
+        if (formats[i] < MTSH_FORMAT_LUMINANCE || formats[i] > MTSH_FORMAT_XYZA) { g_err = "mtsh_develop_multi: unknown format"; return -1; }
+        static const int count[] = {1, 2, 3, 4, 3, 4};
+        per += count[formats[i]];
+    }
+    const size_t src = 3 * (size_t)n + 2;
+    float *dst = out;
+    // Bitmap::convertMultiSpectrumAlphaWeight (bitmap.cpp:1617-1672)
+    for (size_t k = 0; k < (size_t)w * h; ++k) {
+        const float *s = block + k * src;
+        const float weight = s[src - 1], invWeight = weight == 0 ? 0.0f : 1.0f / weight;
+        const float alpha = s[src - 2] * invWeight;
+        for (int i = 0; i < n; ++i) {
+            const float r = s[3 * i] * invWeight, g = s[3 * i + 1] * invWeight, b = s[3 * i + 2] * invWeight;
+            const int f = formats[i];
+            if (f == MTSH_FORMAT_LUMINANCE || f == MTSH_FORMAT_LUMINANCE_ALPHA) {
+                *dst++ = r * 0.212671f + g * 0.715160f + b * 0.072169f;   // spectrum.h:725-727
+            } else if (f == MTSH_FORMAT_XYZ || f == MTSH_FORMAT_XYZA) {   // spectrum.cpp:229-234
+                *dst++ = r * 0.412453f + g * 0.357580f + b * 0.180423f;
+                *dst++ = r * 0.212671f + g * 0.715160f + b * 0.072169f;
+                *dst++ = r * 0.019334f + g * 0.119193f + b * 0.950227f;
+            } else {
+                *dst++ = r; *dst++ = g; *dst++ = b;
+            }
+            if (f == MTSH_FORMAT_LUMINANCE_ALPHA || f == MTSH_FORMAT_RGBA || f == MTSH_FORMAT_XYZA) *dst++ = alpha;
+        }
+    }
+    return per;
+}
+
+int mtsh_write_exr(const char *path, int w, int h, int n_channels, const char *const *names, const float *data) {
+    if (!path || !names || !data || w <= 0 || h <= 0 || n_channels <= 0) { g_err = "mtsh_write_exr: invalid arguments"; return -1; }
+    try {
+        std::vector<std::string> nm;
+        std::vector<std::vector<float>> planes(n_channels, std::vector<float>((size_t)w * h));
+        std::vector<const float *> ptr;
+        for (int c = 0; c < n_channels; ++c) {
+            if (!names[c] || !*names[c]) throw std::runtime_error("mtsh_write_exr: a channel without a name");
+            nm.push_back(names[c]);
+            for (size_t k = 0; k < (size_t)w * h; ++k) planes[c][k] = data[k * n_channels + c];
+            ptr.push_back(planes[c].data());
+        }
+        mtsh::writeEXR(path, w, h, nm, ptr.data());
+        return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
     }
 }
 

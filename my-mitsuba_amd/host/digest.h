@@ -76,7 +76,7 @@ inline std::vector<mtsh_digest_entry> sceneDigest(const mtsg_scene_desc &d) {
     add("group_indices", d.group_indices, sizeof(uint32_t) * (size_t)d.n_group_indices);
     add("textures", d.textures, sizeof(mtsg_texture) * (size_t)d.n_textures);
     add("tex_texels", d.tex_texels, sizeof(float) * (size_t)d.n_tex_texels);
-    if (d.n_textures) {
+    if (d.n_textures || d.tri_uv) {   // textures, or a multichannel `uv` field
         add("tri_uv", d.tri_uv, sizeof(float) * 6 * (size_t)d.n_triangles);
         add("tri_dpdv", d.tri_dpdv, sizeof(float) * 3 * (size_t)d.n_triangles);
     }

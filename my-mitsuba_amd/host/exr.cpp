@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -438,6 +439,67 @@ bool readEXR(const std::string &path, int &w, int &h, std::vector<float> &rgb, s
         }
     }
     return true;
+}
+
+// OpenEXR scanline output for hdrfilm's multichannel images (hdrfilm.cpp:
+// 328-334 -> Bitmap::writeOpenEXR): version 2, single part, NO_COMPRESSION,
+// increasing Y, one chunk per scanline, FLOAT channels stored in the order of
+// their names as the format requires
+void writeEXR(const std::string &path, int w, int h, const std::vector<std::string> &names, const float *const *planes) {
+    if (w <= 0 || h <= 0 || names.empty()) throw std::runtime_error("writeEXR: empty image");
+    std::vector<size_t> order(names.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return names[a] < names[b]; });
+    for (size_t i = 0; i < order.size(); ++i) {
+        const std::string &n = names[order[i]];
+        if (n.empty() || n.size() > 255) throw std::runtime_error("writeEXR: channel names hold 1 to 255 characters");
+        if (i && n == names[order[i - 1]]) throw std::runtime_error("writeEXR: duplicate channel name \"" + n + "\"");
+    }
+    std::vector<uint8_t> out;
+    auto u8 = [&](uint8_t v) { out.push_back(v); };
+    auto i32 = [&](int32_t v) { for (int k = 0; k < 4; ++k) out.push_back((uint8_t)((uint32_t)v >> (8 * k))); };
+    auto f32 = [&](float v) { uint32_t u; memcpy(&u, &v, 4); i32((int32_t)u); };
+    auto str = [&](const std::string &s) { out.insert(out.end(), s.begin(), s.end()); out.push_back(0); };
+    auto attr = [&](const char *name, const char *type, int32_t size) { str(name); str(type); i32(size); };
+    i32(20000630);   // magic
+    i32(2);          // version 2, no flags
+    int32_t chSize = 1;
+    for (size_t i : order) chSize += (int32_t)names[i].size() + 1 + 16;
+    attr("channels", "chlist", chSize);
+    for (size_t i : order) {
+        str(names[i]);
+        i32(2);                   // FLOAT
+        u8(0); u8(0); u8(0); u8(0);   // pLinear, reserved
+        i32(1); i32(1);           // sampling
+    }
+    u8(0);
+    attr("compression", "compression", 1); u8(0);
+    attr("dataWindow", "box2i", 16); i32(0); i32(0); i32(w - 1); i32(h - 1);
+    attr("displayWindow", "box2i", 16); i32(0); i32(0); i32(w - 1); i32(h - 1);
+    attr("lineOrder", "lineOrder", 1); u8(0);
+    attr("pixelAspectRatio", "float", 4); f32(1.0f);
+    attr("screenWindowCenter", "v2f", 8); f32(0.0f); f32(0.0f);
+    attr("screenWindowWidth", "float", 4); f32(1.0f);
+    u8(0);
+    const size_t lineBytes = (size_t)w * 4 * names.size();
+    const uint64_t first = out.size() + 8 * (uint64_t)h;
+    for (int y = 0; y < h; ++y) {
+        const uint64_t o = first + (uint64_t)y * (8 + lineBytes);
+        for (int k = 0; k < 8; ++k) out.push_back((uint8_t)(o >> (8 * k)));
+    }
+    out.reserve(out.size() + (size_t)h * (8 + lineBytes));
+    for (int y = 0; y < h; ++y) {
+        i32(y);
+        i32((int32_t)lineBytes);
+        for (size_t i : order) {
+            const float *row = planes[i] + (size_t)y * w;
+            for (int x = 0; x < w; ++x) f32(row[x]);
+        }
+    }
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + path);
+    const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+    if (fclose(f) != 0 || !ok) throw std::runtime_error("error writing " + path);
 }
 
 }  // namespace mtsh

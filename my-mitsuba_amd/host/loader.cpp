@@ -335,9 +335,12 @@ void loadPLY(const std::string &path, Mesh &mesh) {
     }
 }
 
-void loadOBJ(const std::string &path, Mesh &mesh, bool flipTexCoords) {
+void loadOBJ(const std::string &path, Mesh &mesh, bool flipTexCoords, bool collapse) {
     // Simplified obj.cpp: all groups collapsed into one mesh, polygon fans
-    // (obj.cpp:309-322), vertices deduplicated by (p, n, uv) (obj.cpp:577-660)
+    // (obj.cpp:309-322), vertices deduplicated by (p, n, uv) (obj.cpp:577-660).
+    // The reference flushes one TriMesh per `g` / `usemtl` that follows faces
+    // (obj.cpp:258-295, unless `collapse`): those boundaries are kept in
+    // mesh.elemStart for the shapeIndex / primIndex fields
     std::ifstream f(path);
     if (!f) throw err("Unable to open \"" + path + "\"");
     std::vector<V3> P, N;
@@ -371,10 +374,16 @@ void loadOBJ(const std::string &path, Mesh &mesh, bool flipTexCoords) {
         verts.push_back(k);
         return id;
     };
+    std::vector<uint32_t> elemStart{0u};
     while (std::getline(f, line)) {
         std::istringstream iss(line);
         std::string t;
         if (!(iss >> t)) continue;
+        if ((t == "g" || t == "usemtl") && !collapse) {
+            const uint32_t nTri = (uint32_t)(idx.size() / 3);
+            if (nTri > elemStart.back()) elemStart.push_back(nTri);
+            continue;
+        }
         if (t == "v") { V3 v; iss >> v.x >> v.y >> v.z; P.push_back(v); }
         else if (t == "vn") { V3 v; iss >> v.x >> v.y >> v.z; N.push_back(v); }
         else if (t == "vt") { float u = 0, v = 0; iss >> u >> v; if (flipTexCoords) v = 1 - v; T.emplace_back(u, v); }
@@ -402,6 +411,8 @@ void loadOBJ(const std::string &path, Mesh &mesh, bool flipTexCoords) {
         if (anyN) mesh.n[i] = (k.n > 0 && (size_t)k.n <= N.size()) ? N[k.n - 1] : V3(0.0f);
         if (anyT && k.t > 0 && (size_t)k.t <= T.size()) { mesh.uv[2 * i] = T[k.t - 1].first; mesh.uv[2 * i + 1] = T[k.t - 1].second; }
     }
+    if (elemStart.size() > 1 && elemStart.back() == idx.size() / 3) elemStart.pop_back();   // a trailing group without faces
+    if (elemStart.size() > 1) mesh.elemStart = elemStart;
     mesh.idx = std::move(idx);
 }
 
@@ -834,6 +845,19 @@ struct Loader {
                 Properties props;
                 std::vector<XNode *> nested;
                 parseProps(c, props, nested);
+                // multichannel's nested integrators, in document order
+                // (MultiChannelIntegrator::addChild, multichannel.cpp:219-231)
+                for (XNode *k : nested) {
+                    substAll(*k);
+                    if (k->tag != "integrator" || lower(c.attr("type")) != "multichannel")
+                        throw err("line " + std::to_string(k->line) + ": unsupported element <" + k->tag + "> inside this <integrator>");
+                    Properties kp;
+                    std::vector<XNode *> kn;
+                    parseProps(*k, kp, kn);
+                    if (!kn.empty() && lower(k->attr("type")) != "multichannel")
+                        throw err("line " + std::to_string(k->line) + ": multichannel: a child integrator with nested objects is not supported");
+                    B.integratorChild(k->attr("type"), kp, k->line);
+                }
                 B.integrator(c.attr("type"), props, c.line);
             } else if (tag == "sensor" || tag == "camera") {
                 parseSensor(c);

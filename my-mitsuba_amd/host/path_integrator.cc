@@ -34,6 +34,7 @@ std::string device_error() {
 struct mtsh_path_job {
     std::vector<mtsg_scene *> handles;
     int border = 0;
+    int multiChannels = 0;   // 3m + 2 floats per texel of a multichannel scene's block (0: the 5-channel `path` film)
     // cancel(): the job's flag is checked by each worker before its render
     // starts; the handles' flags stop renders already running (per bounce)
     std::atomic<int> cancel{0};
@@ -144,6 +145,16 @@ int mtsh_path_job_create(const mtsh_scene *scene, int n_gpus, mtsh_path_job **ou
             mtsh_path_job_destroy(job);
             return rc;
         }
+        // a multichannel scene: its child set on every GPU (mtsh_path_job_render_multi)
+        if (const mtsg_aov_desc *aov = mtsh_scene_aov(scene)) {
+            const int rca = mtsg_scene_set_aov(job->handles[g], aov);
+            if (rca != MTSG_OK) {
+                g_perr = "GPU " + std::to_string(g) + ": " + device_error();
+                mtsh_path_job_destroy(job);
+                return rca;
+            }
+            job->multiChannels = 3 * (int)aov->n_children + 2;
+        }
     }
     *out = job;
     return MTSG_OK;
@@ -167,9 +178,19 @@ int mtsh_path_job_set_tile_callback(mtsh_path_job *job, mtsh_path_tile_fn fn, vo
     return MTSG_OK;
 }
 
-int mtsh_path_job_render(mtsh_path_job *job, const mtsg_render_params *params, float *rgbaw_out,
-                         double *seconds_out) {
+}  // extern "C"
+
+namespace {
+// the job's render over CH floats per texel: 5 (mtsg_render) or a multichannel
+// scene's 3m + 2 (mtsg_render_multi); the GPUs' blocks are summed alike
+int job_render(mtsh_path_job *job, const mtsg_render_params *params, float *rgbaw_out, double *seconds_out, bool multi) {
     if (!job || !params || !rgbaw_out) { g_perr = "null argument"; return MTSG_ERR_INVALID; }
+    if (multi != (job->multiChannels != 0)) {
+        g_perr = multi ? "the job's scene is not multichannel"
+                       : "the job's scene is multichannel: use mtsh_path_job_render_multi (channels are not dropped)";
+        return MTSG_ERR_INVALID;
+    }
+    const size_t CH = multi ? (size_t)job->multiChannels : 5;
     std::lock_guard<std::mutex> lock(job->renderLock);
     const int n = (int)job->handles.size();
     const int b = job->border;
@@ -208,7 +229,7 @@ int mtsh_path_job_render(mtsh_path_job *job, const mtsg_render_params *params, f
         share[g].assign(order.begin() + lo, order.begin() + lo + count[g]);
         std::sort(share[g].begin(), share[g].end());
     }
-    std::vector<std::vector<float>> blocks(n, std::vector<float>(W * H * 5));
+    std::vector<std::vector<float>> blocks(n, std::vector<float>(W * H * CH));
     std::vector<int> rcs(n, MTSG_OK);
     std::vector<double> sec(n, 0.0);
     std::vector<std::string> errs(n);
@@ -229,7 +250,8 @@ int mtsh_path_job_render(mtsh_path_job *job, const mtsg_render_params *params, f
             else if (share[g].empty()) rcs[g] = MTSG_OK;   // fewer tiles than GPUs: this one idles
             else if ((rcs[g] = mtsg_set_tile_list(job->handles[g], share[g].data(), (uint32_t)share[g].size())) == MTSG_OK) {
                 const auto tg = std::chrono::steady_clock::now();
-                rcs[g] = mtsg_render(job->handles[g], &p, blocks[g].data());
+                rcs[g] = multi ? mtsg_render_multi(job->handles[g], &p, blocks[g].data())
+                               : mtsg_render(job->handles[g], &p, blocks[g].data());
                 sec[g] = std::chrono::duration<double>(std::chrono::steady_clock::now() - tg).count();
             }
             {
@@ -254,9 +276,9 @@ int mtsh_path_job_render(mtsh_path_job *job, const mtsg_render_params *params, f
             g_perr = "cancelled";
             return MTSG_ERR_CANCELLED;
         }
-    std::memset(rgbaw_out, 0, W * H * 5 * sizeof(float));
+    std::memset(rgbaw_out, 0, W * H * CH * sizeof(float));
     for (int g = 0; g < n; ++g)
-        for (size_t i = 0; i < W * H * 5; ++i) rgbaw_out[i] += blocks[g][i];
+        for (size_t i = 0; i < W * H * CH; ++i) rgbaw_out[i] += blocks[g][i];
     // a GPU whose share grew past any it rendered before may have spent part
     // of its time allocating: that render keeps the cut (no re-cut from it)
     bool grew = false;
@@ -268,6 +290,17 @@ int mtsh_path_job_render(mtsh_path_job *job, const mtsg_render_params *params, f
     job->lastCount = count;
     job->lastSec = sec;
     return MTSG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mtsh_path_job_render(mtsh_path_job *job, const mtsg_render_params *params, float *rgbaw_out, double *seconds_out) {
+    return job_render(job, params, rgbaw_out, seconds_out, false);
+}
+
+int mtsh_path_job_render_multi(mtsh_path_job *job, const mtsg_render_params *params, float *block_out, double *seconds_out) {
+    return job_render(job, params, block_out, seconds_out, true);
 }
 
 int mtsh_path_job_set_balance(mtsh_path_job *job, int on) {

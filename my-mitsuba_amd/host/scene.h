@@ -48,6 +48,10 @@ struct Mesh {
     int bsdf = -1, emitter = -1;
     int group = -1;                  // two-level: the shape group it belongs to (group space)
     bool instanced = false;          // flattened from an instance (not a Scene::getMeshes() TriMesh)
+    // a compound shape's elements (an `obj` with several groups is one Mesh
+    // here and one TriMesh per group in Scene::m_shapes, obj.cpp:258-295,787-800):
+    // the local triangle each element starts at; empty = one element
+    std::vector<uint32_t> elemStart;
 };
 
 struct Rect {
@@ -82,6 +86,9 @@ struct Texture {
 struct ShapeRef {                    // m_shapes order in the kd-tree
     int type;                        // MTSG_SHAPE_*
     int index;                       // into meshes / rects / instances
+    // position of the shape (its first element) in Mitsuba's Scene::m_shapes
+    // after initialize (scene.cpp:345-357,608-647); -1: instanced geometry
+    int sceneIndex = -1;
 };
 
 // Two-level instancing (src/shapes/shapegroup.cpp, instance.cpp)
@@ -109,6 +116,9 @@ struct Film {
     float stddev = 0.5f, boxRadius = 0.5f;
     bool hasAlpha = false;
     std::string pixelFormat = "rgb";
+    // hdrfilm's pixelFormat / channelNames lists (hdrfilm.cpp:216-295): one
+    // entry per child of a multichannel integrator
+    std::vector<std::string> pixelFormats{"rgb"}, channelNames;
 };
 
 struct IntegratorProps {
@@ -118,6 +128,11 @@ struct IntegratorProps {
     // myPath2_OM (myPath2_OM.cpp:61-85)
     int omStrategy = MTSG_OM_STRATEGY_MIS, omMis = MTSG_OM_MIS_BALANCE;
     bool omJitter = true;
+    // multichannel (multichannel.cpp:87-243): its children in order, each
+    // `path` or a `field` (field.cpp:55-110)
+    bool multichannel = false;
+    struct Child { int kind; V3 undefined; };   // MTSG_AOV_PATH / MTSG_FIELD_*
+    std::vector<Child> children;
 };
 
 struct KDBuildParams {                // gkdtree.h:734-744 defaults, except stopPrims
@@ -193,6 +208,12 @@ struct Scene {
     std::vector<uint32_t> groupIndices;
     mtsg_camera camera{};
     mtsg_scene_desc desc{};
+    // multichannel scenes (buildAov): the descriptor beside `desc` and its tables
+    std::vector<mtsg_aov_bsdf> aovBsdfs;
+    std::vector<mtsg_aov_shape> aovShapes;
+    std::vector<uint32_t> aovElems;
+    mtsg_aov_desc aovDesc{};
+    void buildAov();
 
     std::vector<uint8_t> triGrouped;  // triangle lives in a shape group's own tree (two-level)
 
@@ -282,6 +303,10 @@ public:
     int group(const std::string &id);
     void instance(int group, const Transform &toWorld);
     void integrator(const std::string &type, const Properties &props, int line = 0);
+    // a child of the multichannel integrator, in order (returns its position),
+    // then the parent, which takes the children added so far
+    int integratorChild(const std::string &type, const Properties &props, int line = 0);
+    void multichannel(const Properties &props, int line = 0);
     void sensor(const std::string &type, const Properties &props, int line = 0);
     void film(const std::string &type, const Properties &props);
     void rfilter(const std::string &type, const Properties &props);
@@ -293,6 +318,11 @@ private:
     Scene &scene;
     std::vector<ShapeGroup> groups;
     std::set<int> claimed;   // area emitters attached to a shape
+    int nextSceneIndex = 0;  // Scene::m_shapes position of the next top-level shape
+    int curSceneIndex = -1;  // ... of the shape being added (-1: instanced geometry)
+    std::vector<IntegratorProps::Child> pendingChildren;
+    IntegratorProps pendingPath;   // the `path` child's own properties
+    bool havePendingPath = false;
     V3 reflectance(const Properties &props, int tex, const V3 &constant, mtsg_bsdf &d, float &maxOut);
     int defaultBsdf(bool emitter);
     void checkEmitter(int emitter, bool inGroup, bool claim);
@@ -310,7 +340,7 @@ std::unique_ptr<Scene> loadScene(const std::string &path,
 
 // Mesh loaders
 void loadPLY(const std::string &path, Mesh &mesh);   // src/shapes/ply.cpp
-void loadOBJ(const std::string &path, Mesh &mesh, bool flipTexCoords);  // src/shapes/obj.cpp
+void loadOBJ(const std::string &path, Mesh &mesh, bool flipTexCoords, bool collapse = false);  // src/shapes/obj.cpp
 void loadSerialized(const std::string &path, int shapeIndex, Mesh &mesh);  // src/shapes/serialized.cpp
 
 // TriMesh::computeNormals (src/librender/trimesh.cpp:608-681)
@@ -338,5 +368,12 @@ float roughDiffuseTransmittance(int type, float alpha, float eta);
 
 // Film developing (hdrfilm.cpp:481-492, fmtconv.cpp:962-974) and PFM output
 void writePFM(const std::string &path, int w, int h, const std::vector<float> &rgb);
+// OpenEXR scanline output, uncompressed FLOAT channels (exr.cpp): planes[c] is
+// channel names[c], w * h floats, rows top-down
+void writeEXR(const std::string &path, int w, int h, const std::vector<std::string> &names, const float *const *planes);
+// hdrfilm's channel names and per-entry channel counts for a pixelFormat list
+// (hdrfilm.cpp:245-295); throws on an unknown format
+void filmChannels(const std::vector<std::string> &formats, const std::vector<std::string> &names, std::vector<std::string> &channels,
+                  std::vector<int> &formatIds);
 
 }  // namespace mtsh

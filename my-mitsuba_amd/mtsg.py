@@ -210,6 +210,72 @@ class MeshArrays(C.Structure):
                 ("to_world_inv", C.c_void_p)]
 
 
+MAX_SUBINTEGRATORS = 8
+AOV_PATH = 0
+FIELD_IDS = {"position": 1, "relPosition": 2, "distance": 3, "geoNormal": 4, "shNormal": 5, "uv": 6, "albedo": 7,
+             "shapeIndex": 8, "primIndex": 9}
+FORMAT_NAMES = ("luminance", "luminanceAlpha", "rgb", "rgba", "xyz", "xyza")   # MTSH_FORMAT_*
+FORMAT_CHANNELS = (1, 2, 3, 4, 3, 4)
+
+
+class AovChild(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("undefined", C.c_float * 3)]
+
+
+class AovBsdf(C.Structure):
+    _fields_ = [("factor", C.c_float * 3), ("textured", C.c_int32)]
+
+
+class AovShape(C.Structure):
+    _fields_ = [("scene_index", C.c_int32), ("elem_offset", C.c_uint32), ("elem_count", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class AovDesc(C.Structure):
+    """mtsg_aov_desc (include/mtsg.h)."""
+    _fields_ = [("n_children", C.c_uint32), ("pad", C.c_uint32), ("children", AovChild * MAX_SUBINTEGRATORS),
+                ("world_to_camera", C.c_float * 16), ("n_bsdfs", C.c_uint32), ("n_shapes", C.c_uint32),
+                ("bsdfs", C.POINTER(AovBsdf)), ("shapes", C.POINTER(AovShape)), ("n_elems", C.c_uint32),
+                ("pad2", C.c_uint32), ("elem_starts", C.POINTER(C.c_uint32))]
+
+
+class Aov:
+    """A multichannel scene's child set (Scene.aov()): the descriptor
+    (mtsh_scene_aov) with its tables as arrays, and the film's entries."""
+
+    def __init__(self, scene: "Scene", desc: "C.POINTER(AovDesc)"):
+        d = desc.contents
+        self._scene = scene   # owns the descriptor's memory
+        self.desc = desc
+        self.m = int(d.n_children)
+        self.children = [(int(d.children[k].kind), tuple(float(x) for x in d.children[k].undefined)) for k in range(self.m)]
+        self.path_child = next((k for k, c in enumerate(self.children) if c[0] == AOV_PATH), -1)
+        self.world_to_camera = np.array(list(d.world_to_camera), np.float32).reshape(4, 4)
+        self.bsdf_factor = np.array([list(d.bsdfs[i].factor) for i in range(d.n_bsdfs)], np.float32).reshape(-1, 3)
+        self.bsdf_textured = np.array([d.bsdfs[i].textured for i in range(d.n_bsdfs)], np.int32)
+        self.shape_scene_index = np.array([d.shapes[i].scene_index for i in range(d.n_shapes)], np.int32)
+        self.shape_elems = [[int(d.elem_starts[d.shapes[i].elem_offset + e]) for e in range(d.shapes[i].elem_count)]
+                            for i in range(d.n_shapes)]
+        lib = host_lib()
+        n = lib.mtsh_scene_film_formats(scene._h, None, 0)
+        f = (C.c_int32 * max(1, n))()
+        lib.mtsh_scene_film_formats(scene._h, f, n)
+        self.formats = [int(x) for x in f[:n]]
+        buf = C.create_string_buffer(4096)
+        nc = lib.mtsh_scene_film_channels(scene._h, buf, 4096)
+        if nc < 0:
+            raise RuntimeError(_err(lib, "mtsh_last_error"))
+        self.channels = [c.decode() for c in buf.raw.split(b"\0")[:nc]]
+
+    def to_bytes(self) -> bytes:
+        """The descriptor's content (scalars and tables, no addresses): equal
+        bytes = equal descriptors."""
+        d = self.desc.contents
+        head = bytes(C.string_at(C.addressof(d), AovDesc.bsdfs.offset))
+        return b"".join([head, C.string_at(d.bsdfs, C.sizeof(AovBsdf) * d.n_bsdfs) if d.n_bsdfs else b"",
+                         C.string_at(d.shapes, C.sizeof(AovShape) * d.n_shapes) if d.n_shapes else b"",
+                         C.string_at(d.elem_starts, 4 * d.n_elems) if d.n_elems else b""])
+
+
 class DigestEntry(C.Structure):
     """mtsh_digest_entry."""
     _fields_ = [("name", C.c_char * 32), ("bytes", C.c_uint64), ("hash", C.c_uint64)]
@@ -230,6 +296,8 @@ DEVICE_SYMBOLS = [
     "mtsg_last_error", "mtsg_env_eval", "mtsg_tex_eval", "mtsg_om_query", "mtsg_kd_build", "mtsg_kd_refit", "mtsg_kd_free",
     "mtsg_sampler_draws", "mtsg_debug_wavetimes", "mtsg_set_tile_callback",
     "mtsg_debug_stragglers", "mtsg_set_test_knobs", "mtsg_set_option",
+    "mtsg_scene_set_aov", "mtsg_render_multi", "mtsg_render_device_multi", "mtsg_render_device_tiles_multi",
+    "mtsg_render_samples_multi",
 ]
 HOST_SYMBOLS = [
     "mtsh_scene_load", "mtsh_scene_load_overrides", "mtsh_scene_load_props", "mtsh_scene_set_scene_props", "mtsh_set_kd_threads", "mtsh_set_instancing", "mtsh_scene_desc", "mtsh_scene_render_params",
@@ -239,11 +307,13 @@ HOST_SYMBOLS = [
     "mtsh_scene_begin", "mtsh_scene_add_texture", "mtsh_scene_add_bsdf", "mtsh_scene_add_emitter", "mtsh_scene_add_group",
     "mtsh_scene_add_shape", "mtsh_scene_add_mesh", "mtsh_scene_add_instance", "mtsh_scene_set_sensor", "mtsh_scene_set_film",
     "mtsh_scene_set_sampler", "mtsh_scene_set_integrator", "mtsh_scene_finish", "mtsh_scene_abort", "mtsh_scene_digest",
+    "mtsh_scene_add_integrator_child", "mtsh_scene_set_multichannel", "mtsh_scene_aov", "mtsh_scene_film_formats",
+    "mtsh_scene_film_channels", "mtsh_develop_multi", "mtsh_write_exr",
 ]
 PATH_SYMBOLS = [
     "mtsh_path_job_create", "mtsh_path_job_gpus", "mtsh_path_job_render", "mtsh_path_job_cancel",
     "mtsh_path_job_destroy", "mtsh_path_render", "mtsh_path_last_error", "mtsh_path_job_set_tile_callback",
-    "mtsh_path_job_set_balance", "mtsh_path_job_shares",
+    "mtsh_path_job_set_balance", "mtsh_path_job_shares", "mtsh_path_job_render_multi",
 ]
 
 # tile completion hooks (mtsg_set_tile_callback, mtsh_path_job_set_tile_callback)
@@ -271,6 +341,8 @@ def path_lib() -> C.CDLL:
         lib.mtsh_path_job_shares.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mtsh_path_render.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_int, C.c_void_p,
                                          C.POINTER(C.c_double)]
+        lib.mtsh_path_job_render_multi.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p,
+                                                   C.POINTER(C.c_double)]
         lib.mtsh_path_last_error.argtypes = [C.c_char_p, C.c_size_t]
         _path = lib
     return _path
@@ -339,6 +411,16 @@ def host_lib() -> C.CDLL:
         lib.mtsh_scene_abort.argtypes = [C.c_void_p]
         lib.mtsh_scene_digest.restype = C.c_int32
         lib.mtsh_scene_digest.argtypes = [C.c_void_p, C.POINTER(DigestEntry), C.c_int32]
+        lib.mtsh_scene_add_integrator_child.restype = C.c_int32
+        lib.mtsh_scene_add_integrator_child.argtypes = [C.c_void_p, C.c_char_p, PP, C.c_int32]
+        lib.mtsh_scene_set_multichannel.restype = C.c_int32
+        lib.mtsh_scene_set_multichannel.argtypes = [C.c_void_p, PP, C.c_int32]
+        lib.mtsh_scene_aov.restype = C.POINTER(AovDesc)
+        lib.mtsh_scene_aov.argtypes = [C.c_void_p]
+        lib.mtsh_scene_film_formats.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
+        lib.mtsh_scene_film_channels.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        lib.mtsh_develop_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p]
+        lib.mtsh_write_exr.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_void_p]
         _host = lib
     return _host
 
@@ -379,6 +461,10 @@ def device_lib() -> C.CDLL:
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mtsg_trace_shadow.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.mtsg_render_samples.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p]
+        lib.mtsg_scene_set_aov.argtypes = [C.c_void_p, C.POINTER(AovDesc)]
+        for fn in ("mtsg_render_multi", "mtsg_render_device_multi", "mtsg_render_device_tiles_multi",
+                   "mtsg_render_samples_multi"):
+            getattr(lib, fn).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p]
         lib.mtsg_env_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mtsg_tex_eval.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mtsg_kd_build.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(KDBuildParams), C.POINTER(KDTree)]
@@ -513,6 +599,11 @@ class Scene:
         if lib.mtsh_scene_om(self._h, C.byref(hdr), _ptr(bits), bits.size) != 0:
             raise RuntimeError(_err(lib, "mtsh_last_error"))
         return hdr, bits
+
+    def aov(self) -> "Aov | None":
+        """The multichannel child set (mtsh_scene_aov), None for plain scenes."""
+        d = host_lib().mtsh_scene_aov(self._h)
+        return Aov(self, d) if d else None
 
     def textures(self) -> list:
         """The scene's bitmap texture headers (TextureHeader)."""
@@ -651,6 +742,16 @@ class SceneBuilder:
         a, n, _k = _props(props)
         self._rc(host_lib().mtsh_scene_set_integrator(self._b, plugin.encode(), a, n), plugin)
 
+    def integrator_child(self, plugin: str, props) -> int:
+        """A nested integrator of `multichannel` (`path` or `field`), in order."""
+        a, n, _k = _props(props)
+        return self._rc(host_lib().mtsh_scene_add_integrator_child(self._b, plugin.encode(), a, n), plugin)
+
+    def multichannel(self, props=()) -> None:
+        """The `multichannel` parent of the children added so far."""
+        a, n, _k = _props(props)
+        self._rc(host_lib().mtsh_scene_set_multichannel(self._b, a, n), "multichannel")
+
     def scene_props(self, props) -> None:
         """The Scene's own Properties (mtsh_scene_set_scene_props): kd build parameters."""
         a, n, _k = _props(_scene_prop_list(props))
@@ -750,6 +851,33 @@ def develop(rgbaw: np.ndarray) -> np.ndarray:
     return out
 
 
+def develop_multi(block: np.ndarray, formats) -> np.ndarray:
+    """hdrfilm develop of a multichannel block (h, w, 3m + 2) into (h, w, C)
+    (mtsh_develop_multi; Bitmap::convertMultiSpectrumAlphaWeight).  formats:
+    one MTSH_FORMAT_* id or FORMAT_NAMES entry per child."""
+    block = np.ascontiguousarray(block, dtype=np.float32)
+    ids = [FORMAT_NAMES.index(f) if isinstance(f, str) else int(f) for f in formats]
+    h, w, ch = block.shape
+    if ch != 3 * len(ids) + 2:
+        raise ValueError(f"a block of {ch} floats per texel does not hold {len(ids)} children")
+    out = np.zeros((h, w, sum(FORMAT_CHANNELS[i] for i in ids)), np.float32)
+    arr = (C.c_int32 * len(ids))(*ids)
+    if host_lib().mtsh_develop_multi(_ptr(block), w, h, arr, len(ids), _ptr(out)) != out.shape[2]:
+        raise RuntimeError(_err(host_lib(), "mtsh_last_error"))
+    return out
+
+
+def write_exr(path: str, image: np.ndarray, names) -> None:
+    """(h, w, C) float32 as an uncompressed scanline OpenEXR with FLOAT channels `names` (mtsh_write_exr)."""
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    h, w, ch = image.shape
+    if ch != len(names):
+        raise ValueError("one name per channel")
+    arr = (C.c_char_p * ch)(*[n.encode() for n in names])
+    if host_lib().mtsh_write_exr(path.encode(), w, h, ch, arr, _ptr(image)) != 0:
+        raise RuntimeError(_err(host_lib(), "mtsh_last_error"))
+
+
 def read_image(path: str) -> np.ndarray:
     """OpenEXR / PFM image as (h, w, 3) float32, rows top-down (the envmap loader's reader)."""
     lib = host_lib()
@@ -821,6 +949,34 @@ class GPUScene:
         self._h = h
         self.scene = scene
         self.device = device
+        self._aov = None
+        # a multichannel scene's child set is part of the scene
+        if getattr(scene, "aov", None) is not None and scene.aov() is not None:
+            self.set_aov(scene)
+
+    def set_aov(self, scene: "Scene | None") -> None:
+        """Activate the multichannel child set of `scene` (mtsg_scene_set_aov); None turns it off."""
+        aov = scene.aov() if scene is not None else None
+        if scene is not None and aov is None:
+            raise ValueError("the scene's integrator is not multichannel")
+        self._check(device_lib().mtsg_scene_set_aov(self._h, aov.desc if aov else None), "mtsg_scene_set_aov")
+        self._aov = aov
+
+    def render_multi(self, params: RenderParams, border: int) -> np.ndarray:
+        """The multichannel ImageBlock (h + 2 border, w + 2 border, 3m + 2)."""
+        if self._aov is None:
+            raise RuntimeError("no multichannel child set is active")
+        out = np.zeros((params.tile_h + 2 * border, params.tile_w + 2 * border, 3 * self._aov.m + 2), dtype=np.float32)
+        self._check(device_lib().mtsg_render_multi(self._h, C.byref(params), _ptr(out)), "mtsg_render_multi")
+        return out
+
+    def render_samples_multi(self, params: RenderParams) -> np.ndarray:
+        """Per sample the children's spectra and alpha: (tile_h, tile_w, spp, 3m + 1)."""
+        if self._aov is None:
+            raise RuntimeError("no multichannel child set is active")
+        out = np.zeros((params.tile_h, params.tile_w, params.spp, 3 * self._aov.m + 1), dtype=np.float32)
+        self._check(device_lib().mtsg_render_samples_multi(self._h, C.byref(params), _ptr(out)), "mtsg_render_samples_multi")
+        return out
 
     def _check(self, rc, what):
         if rc != MTSG_OK:
@@ -995,6 +1151,16 @@ class PathJob:
         out = np.zeros((params.tile_h + 2 * border, params.tile_w + 2 * border, 5), dtype=np.float32)
         secs = C.c_double(0.0)
         rc = path_lib().mtsh_path_job_render(self._h, C.byref(params), _ptr(out), C.byref(secs))
+        return rc, out, secs.value
+
+    def render_multi(self, params: RenderParams, border: int) -> tuple[int, np.ndarray, float]:
+        """A multichannel scene: (error code, block of 3m + 2 floats per texel, seconds)."""
+        aov = self.scene.aov()
+        if aov is None:
+            raise RuntimeError("the scene's integrator is not multichannel")
+        out = np.zeros((params.tile_h + 2 * border, params.tile_w + 2 * border, 3 * aov.m + 2), dtype=np.float32)
+        secs = C.c_double(0.0)
+        rc = path_lib().mtsh_path_job_render_multi(self._h, C.byref(params), _ptr(out), C.byref(secs))
         return rc, out, secs.value
 
     def set_balance(self, on: bool) -> None:
