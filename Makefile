@@ -23,7 +23,7 @@ ORACLE      := oracle/liboracle.so
 ORACLE_FAST := oracle/liboracle_fast.so
 
 .PHONY: all host device oracle clean
-all: host device oracle $(PATH_LIB) $(CLI) scenes/sky512.pfm tools/math_probe tools/math_bench tools/div_probe tools/check_glibc_mathf tools/check_env_guide tools/check_multichannel_host
+all: host device oracle $(PATH_LIB) $(CLI) scenes/sky512.pfm tools/math_probe tools/math_bench tools/div_probe tools/check_glibc_mathf tools/check_env_guide tools/check_multichannel_host tools/check_render_plan
 host: $(HOST_LIB)
 device: $(DEV_LIB)
 oracle: $(ORACLE) $(ORACLE_FAST)
@@ -112,6 +112,11 @@ tools/check_env_guide: tools/check_env_guide.cpp $(PKG)/csrc/envmap.h $(HOST_LIB
 tools/check_multichannel_host: tools/check_multichannel_host.cpp $(HOST_SRC) $(HOST_HDR) $(SOBOL_BIN)
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall \
 	    -DMTSH_SOBOL_BIN='"$(SOBOL_BIN)"' -o $@ $< $(HOST_SRC) -lz -lpthread
+
+# the batch plan of a render call (csrc/render_plan.h: host-only integer
+# arithmetic) over a sweep of shapes, under ASan + UBSan (CPU only)
+tools/check_render_plan: tools/check_render_plan.cpp $(PKG)/csrc/render_plan.h
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -o $@ $<
 
 # synthetic HDR environment for the envmap scenes (tools/gen_envmap.py)
 scenes/sky512.pfm: tools/gen_envmap.py

@@ -323,13 +323,29 @@ constexpr uint32_t CNT_ERR_QMC_DIM = 1u, CNT_ERR_TRAVERSAL = 2u;
 constexpr int CNT_FETCH = 256;                           // XGROUPS counters, 32 words apart
 constexpr int CNT_WORDS = CNT_FETCH + 32 * XGROUPS;
 constexpr int HOSTCNT_STRIDE = 256;
-// traversal counters (MTSG_FLAG_COUNT): [0,7) closest, [8,15) shadow (see
-// flush_counts), 7 / 15 the maximum iterations per ray, [16,32) / [32,48)
-// histograms of floor(log2(iterations per ray)); [48] the number of captured
-// stragglers (rays of >= STRAGGLER_ITERS iterations), [64, 64 + 8 * 64) their
-// records (o.xyz, d.xyz, iterations, shadow as float / integer bits)
-constexpr int CTR_WORDS = 64 + 8 * 64;
+// traversal counters (MTSG_FLAG_COUNT): the 64-bit words of DevPaths::ctr.  This
+// enum is the one place that knows the layout: the kernels below write the words
+// and the render's final drain (mtsg.hip) copies them into mtsg_stats by name.
+enum : int {
+    // [0,7) closest, [8,15) shadow: per-lane work and wave-level iterations (flush_counts)
+    CTR_NODES = 0, CTR_REFS, CTR_TESTS, CTR_WAVE_NODE_ITERS, CTR_WAVE_TEST_ITERS, CTR_WAVE_STEPS, CTR_WAVE_ACTIVE,
+    CTR_FLUSHED,                                   // the 7 words above
+    CTR_ITER_MAX = 7,                              // 7 / 15: the maximum iterations per ray
+    CTR_SHADOW = 8,                                // base of the shadow rays' words 0-7
+    CTR_HIST_CLOSEST = 16, CTR_HIST_SHADOW = 32,   // [16,32) / [32,48): histograms of floor(log2(iterations per ray))
+    CTR_HIST_BINS = 16,
+    CTR_STRAGGLERS = 48,                           // captured stragglers (rays of >= STRAGGLER_ITERS iterations)
+    CTR_INST_VISITS = 49,                          // 49 / 50: instance entries of closest / shadow rays (two-level)
+    CTR_TIE_RETRACES = 51,                         // closest rays traced again after an exact tie
+    // flat, + 0 closest, + 1 shadow: rays that took the restart guard's one-ulp step, those steps, all kd-restarts
+    CTR_GUARD_RAYS = 52, CTR_GUARD_STEPS = 54, CTR_RESTARTS = 56,
+    CTR_INST_REJECTS = 58,                         // instance entries the group-box clip rejected (both kinds)
+    CTR_INST_PREFILTERED = 59,                     // instance nodes the prefilter box skipped before any entry
+    // [64, 64 + 8 * 64): the stragglers' records (o.xyz, d.xyz, iterations, shadow as float / integer bits)
+    CTR_STRAGGLER_RECORDS = 64, CTR_STRAGGLER_WORDS = 8,
+};
 constexpr uint32_t STRAGGLER_ITERS = 300, STRAGGLER_MAX = 64;
+constexpr int CTR_WORDS = CTR_STRAGGLER_RECORDS + CTR_STRAGGLER_WORDS * STRAGGLER_MAX;
 constexpr uint32_t WT_MAX_LAUNCHES = 64;   // MTSG_FLAG_WAVETIME launches recorded per render
 // MTSG_FLAG_WAVETIME words per wave: start, exit, time the work list was found
 // empty, loop iterations after that
@@ -503,13 +519,14 @@ template <bool COUNT>
 DEV void flush_counts(unsigned long long *ctr, TraceCounts c) {
     if (!COUNT) return;
     // wave reduction then one atomic per counter per wave
-    unsigned long long v[7] = {c.nodes, c.refs, c.tests, c.wnodes, c.wtests, c.wsteps, c.wactive};
+    // in the order of CTR_NODES .. CTR_WAVE_ACTIVE
+    unsigned long long v[CTR_FLUSHED] = {c.nodes, c.refs, c.tests, c.wnodes, c.wtests, c.wsteps, c.wactive};
 #pragma unroll
-    for (int k = 0; k < 7; ++k)
+    for (int k = 0; k < CTR_FLUSHED; ++k)
         for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off);
     if (lane_id() == 0)
 #pragma unroll
-        for (int k = 0; k < 7; ++k) atomicAdd(ctr + k, v[k]);
+        for (int k = 0; k < CTR_FLUSHED; ++k) atomicAdd(ctr + k, v[k]);
 }
 
 #ifndef MTSG_FETCH
@@ -1418,7 +1435,7 @@ DEV bool spec_iter_i(const DevScene &S, SpecRay &r, TraceCounts &cnt, const DevP
         const float4 A1 = make_float4(__uint_as_float(pc.x), __uint_as_float(pc.y), __uint_as_float(pc.z), __uint_as_float(pc.w));
         if (inst_enter(r, ts, S, inst, f0, f1, f2, A0, A1)) return false;
         // COUNT: entries the group-box clip rejected (stats.instance_rejects)
-        if (COUNT) atomicAdd(P.ctr + 58, 1ull);
+        if (COUNT) atomicAdd(P.ctr + CTR_INST_REJECTS, 1ull);
         // not entered: the leaf logic below, as after the primitive step
     }
     bool enter = false;
@@ -1435,7 +1452,7 @@ DEV bool spec_iter_i(const DevScene &S, SpecRay &r, TraceCounts &cnt, const DevP
 #if MTSG_INST_PREFILTER
         if (isInst) {
             enter = !L.prefilter || inst_box(r, f0, f1);
-            if (COUNT && !enter) atomicAdd(P.ctr + 59, 1ull);   // stats.instance_prefiltered
+            if (COUNT && !enter) atomicAdd(P.ctr + CTR_INST_PREFILTERED, 1ull);   // stats.instance_prefiltered
         }
 #endif
         if (COUNT && !defer) cnt.refs++;
@@ -1918,7 +1935,7 @@ k_trace_s(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned
         }
         if (COUNT && active) ++iters;
         if (done && MTSG_MAILBOX && (r.bits & (SB_TIE | SB_SHADOW | SB_MBRUN)) == SB_TIE) {
-            if (COUNT) atomicAdd(&P.ctr[51], 1ull);
+            if (COUNT) atomicAdd(&P.ctr[CTR_TIE_RETRACES], 1ull);
             if (!INST && TIE_INLINE) {
                 // a closest ray that met an exact tie is traced again from its
                 // start in this lane with the mailbox (tie_retrace), inside the
@@ -1941,18 +1958,18 @@ k_trace_s(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned
                     // kd-restarts of the ray, and those that took the guard's
                     // one-ulp step (restart number >= rstGuard, kd_restart)
                     const uint32_t nr = (r.bits >> SB_RST_SHIFT) & SB_RST_MASK;
-                    if (nr) atomicAdd(&P.ctr[56 + sh], (unsigned long long)nr);
+                    if (nr) atomicAdd(&P.ctr[CTR_RESTARTS + sh], (unsigned long long)nr);
                     if (nr > L.rstGuard) {
-                        atomicAdd(&P.ctr[52 + sh], 1ull);
-                        atomicAdd(&P.ctr[54 + sh], (unsigned long long)(nr - L.rstGuard));
+                        atomicAdd(&P.ctr[CTR_GUARD_RAYS + sh], 1ull);
+                        atomicAdd(&P.ctr[CTR_GUARD_STEPS + sh], (unsigned long long)(nr - L.rstGuard));
                     }
                 }
-                atomicMax(&P.ctr[sh ? 15 : 7], (unsigned long long)iters);
-                atomicAdd(&P.ctr[(sh ? 32 : 16) + min(15, 31 - __clz(max(iters, 1u)))], 1ull);
+                atomicMax(&P.ctr[sh ? CTR_SHADOW + CTR_ITER_MAX : CTR_ITER_MAX], (unsigned long long)iters);
+                atomicAdd(&P.ctr[(sh ? CTR_HIST_SHADOW : CTR_HIST_CLOSEST) + min(CTR_HIST_BINS - 1, 31 - __clz(max(iters, 1u)))], 1ull);
                 if (iters >= STRAGGLER_ITERS) {
-                    const unsigned long long k = atomicAdd(&P.ctr[48], 1ull);
+                    const unsigned long long k = atomicAdd(&P.ctr[CTR_STRAGGLERS], 1ull);
                     if (k < STRAGGLER_MAX) {
-                        unsigned long long *o = P.ctr + 64 + 8 * k;
+                        unsigned long long *o = P.ctr + CTR_STRAGGLER_RECORDS + CTR_STRAGGLER_WORDS * k;
                         o[0] = __float_as_uint(r.o.x); o[1] = __float_as_uint(r.o.y); o[2] = __float_as_uint(r.o.z);
                         o[3] = __float_as_uint(r.d.x); o[4] = __float_as_uint(r.d.y); o[5] = __float_as_uint(r.d.z);
                         const TraceCounts &kk = sh ? cs : cc;
@@ -1970,12 +1987,12 @@ k_trace_s(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned
         }
     }
     flush_counts<COUNT>(P.ctr, cc);
-    flush_counts<COUNT>(P.ctr + 8, cs);
+    flush_counts<COUNT>(P.ctr + CTR_SHADOW, cs);
     if (COUNT && INST) {
         unsigned long long vi[2] = {cc.inst, cs.inst};
         for (int k = 0; k < 2; ++k) {
             for (int o2 = 32; o2 > 0; o2 >>= 1) vi[k] += __shfl_down(vi[k], o2);
-            if (lane_id() == 0) atomicAdd(P.ctr + 49 + k, vi[k]);
+            if (lane_id() == 0) atomicAdd(P.ctr + CTR_INST_VISITS + k, vi[k]);
         }
     }
     if (wt && __lane_id() == 0) {

@@ -37,6 +37,9 @@
 #include "sampler.h"
 
 #include "kernels.h"
+#include "render_plan.h"
+
+static_assert(PLAN_TILE == TILE, "render_plan.h plans in tiles of kernels.h's edge");
 
 namespace {
 
@@ -62,6 +65,28 @@ int upload(const T *src, size_t n, T **dst) {
     HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
     return MTSG_OK;
 }
+
+// The scratch buffers of the query entries: n T on the device, freed with the
+// scope.  Every step keeps its failure in the caller's `e` and is skipped once
+// `e` is set, so an entry checks `e` once after its last step.  (The scene's
+// long-lived buffers state their lifetimes themselves: allocs, free_batch,
+// free_aov.)
+template <class T>
+struct DevBuf {
+    hipError_t &e;
+    const size_t n;
+    T *p = nullptr;
+    // n == 0: no buffer (p stays null); src: n T to upload
+    DevBuf(hipError_t &err, size_t count, const T *src = nullptr) : e(err), n(count) {
+        if (e == hipSuccess && n) e = hipMalloc((void **)&p, n * sizeof(T));
+        if (e == hipSuccess && n && src) e = hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    ~DevBuf() { hipFree(p); }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    void zero() { if (e == hipSuccess && n) e = hipMemset(p, 0, n * sizeof(T)); }
+    void download(T *dst) { if (e == hipSuccess && n) e = hipMemcpy(dst, p, n * sizeof(T), hipMemcpyDeviceToHost); }
+};
 
 }  // namespace
 
@@ -299,6 +324,21 @@ void launch_finish(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B, con
         default: launch_finish_smp<MTSG_SAMPLER_INDEPENDENT>(a);
     }
 }
+// k_splat<K, C>: the reconstruction filter's footprint of K x K texels (5, up
+// to 3, or up to 9) and C floats per texel (5 with the film's alpha channel)
+void launch_splat(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B, const DevPaths &P, float *film, int blockW, int blockH,
+                  int win, hipStream_t st) {
+    const dim3 g(B.ntiles, (B.ns + SPLAT_CHUNK - 1) / SPLAT_CHUNK);
+    const int K = 2 * s->cam.border + 1;
+#define SPLAT(W, C) hipLaunchKernelGGL((k_splat<W, C>), g, dim3(BLOCK), 0, st, s->cam, I, B, P, film, blockW, blockH, win)
+    if (K == 5 && !s->cam.has_alpha) SPLAT(5, 4);
+    else if (K == 5) SPLAT(5, 5);
+    else if (K <= 3 && !s->cam.has_alpha) SPLAT(3, 4);
+    else if (K <= 3) SPLAT(3, 5);
+    else if (!s->cam.has_alpha) SPLAT(9, 4);
+    else SPLAT(9, 5);
+#undef SPLAT
+}
 
 // Sampler constants of a render (setFilmResolution with blocked = true over
 // the film's crop size: halton.cpp:240-271, hammersley.cpp:181-200)
@@ -373,10 +413,6 @@ int ensure_fields(mtsg_scene *s) {
     s->fieldCount = nf;
     return MTSG_OK;
 }
-FieldsLaunch fields_args(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B, const DevPaths &P, hipStream_t st, float *film,
-                         int blockW, int blockH, int win) {
-    return FieldsLaunch{st, &s->ds, &s->cam, &I, &B, &P, &s->aov, film, blockW, blockH, win};
-}
 void free_aov(mtsg_scene *s) {
     for (void *p : s->aovAllocs) hipFree(p);
     s->aovAllocs.clear();
@@ -429,292 +465,217 @@ int validate(const mtsg_render_params *p, const mtsg_scene *s) {
     return MTSG_OK;
 }
 
+// The paths a render keeps in flight over all lanes: the requested batch, or
+// the default fitted to the free HBM (stateBytes per path)
+uint32_t fit_paths(const mtsg_scene *s, size_t stateBytes) {
+    if (s->requestedBatch) return s->requestedBatch;
+    uint32_t maxPaths = DEFAULT_BATCH_PATHS;
+    size_t freeB = 0, totalB = 0;
+    if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
+        const size_t held = (size_t)s->capacity * s->lanesAlloc * PATH_STATE_BYTES + (size_t)s->fieldCap * s->fieldCount * 3 * sizeof(float);
+        // 3/4 of the free HBM (288 GB on an MI355X: 768M paths, C5's three
+        // batches of 713M); the rest stays for the scene and other users
+        const size_t fit = (size_t)((freeB + held) * 0.75 / stateBytes);
+        maxPaths = (uint32_t)std::max<size_t>(TILE * TILE, std::min<size_t>(maxPaths, fit));
+    }
+    return maxPaths;
+}
+
+// One render call: the batches of its plan (render_plan.h), plan.lanes at a
+// time, each on its lane's stream and issued bounce by bounce in lock step.
+// Bounce b of a lane: one trace launch over this bounce's closest rays (work
+// list qin(b), identity for b = 0) and bounce b-1's shadow rays (S((b-1) & 1)),
+// then k_shade appends the next bounce's paths to qout(b) = (b & 1) ^ 1 and
+// its shadow rays to S(b & 1).
 // win = 0: film is the ImageBlock of the whole rectangle + border; win > 0:
 // film holds one win x win window per tile of this call (mtsg_render_device_tiles)
-int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win = 0, bool multi = false) {
-    int rc;
-    if ((rc = validate(p, s)) != MTSG_OK) return rc;
-    // a handle with a multichannel child set renders through the *_multi
-    // entries only (3m + 2 floats per texel), a plain handle through the others
-    if (s->aovOn && !multi) {
-        g_err = "the scene's integrator is multichannel: use the _multi render entries (channels are not dropped)";
-        return MTSG_ERR_INVALID;
-    }
-    if (multi && !s->aovOn) { g_err = "no multichannel child set is active (mtsg_scene_set_aov)"; return MTSG_ERR_INVALID; }
-    if (multi && p->integrator != MTSG_INTEGRATOR_PATH) { g_err = "multichannel: only `path` and `field` children"; return MTSG_ERR_INVALID; }
-    if ((rc = set_device(s)) != MTSG_OK) return rc;
-    // bytes of state per path: the field planes join it while fields are active
-    const size_t stateBytes = PATH_STATE_BYTES + (multi ? (size_t)s->aov.nf * 3 * sizeof(float) : 0);
-    auto t0 = std::chrono::steady_clock::now();
-    const bool count = (s->flags & MTSG_FLAG_COUNT) != 0;
-    uint32_t maxPaths = s->requestedBatch ? s->requestedBatch : DEFAULT_BATCH_PATHS;
-    if (!s->requestedBatch) {
-        size_t freeB = 0, totalB = 0;
-        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-            const size_t held = (size_t)s->capacity * s->lanesAlloc * PATH_STATE_BYTES + (size_t)s->fieldCap * s->fieldCount * 3 * sizeof(float);
-            // 3/4 of the free HBM (288 GB on an MI355X: 768M paths, C5's three
-            // batches of 713M); the rest stays for the scene and other users
-            const size_t fit = (size_t)((freeB + held) * 0.75 / stateBytes);
-            maxPaths = (uint32_t)std::max<size_t>(TILE * TILE, std::min<size_t>(maxPaths, fit));
-        }
-    }
-    if ((s->dumpL || s->dumpMulti) && (uint64_t)p->tile_w * p->tile_h * p->spp > maxPaths) { g_err = "render_samples: tile does not fit one batch"; return MTSG_ERR_INVALID; }
-    const uint32_t tilesX = (uint32_t)(p->tile_w + TILE - 1) / TILE, tilesY = (uint32_t)(p->tile_h + TILE - 1) / TILE;
-    const uint32_t allTiles = tilesX * tilesY;
-    const uint32_t tstride = p->tile_stride > 1 ? (uint32_t)p->tile_stride : 1u;
-    const uint32_t toffset = p->tile_stride > 1 ? (uint32_t)p->tile_offset : 0u;
-    const bool listed = !s->tileKeys.empty();
-    const uint32_t ntiles = listed ? (uint32_t)s->tileKeys.size() : toffset < allTiles ? (allTiles - toffset + tstride - 1) / tstride : 0u;
-    if (listed)
-        for (int32_t k : s->tileKeys)
-            if ((uint32_t)k >= allTiles) { g_err = "tile list: a deal key lies outside the rectangle's tiles"; return MTSG_ERR_INVALID; }
-    // the deal key of virtual tile v, on the host
-    auto hostKey = [&](int v) { return listed ? s->tileKeys[v] : (int)toffset + v * (int)tstride; };
-    // Lanes: independent batches on their own streams, issued bounce by bounce
-    // in lock step, so one lane's launch tail (its slowest rays) overlaps the
-    // other lane's launch.  The debug and counting modes use one lane.
-    // (multichannel too: one set of field planes)
-    const uint32_t nl = (s->dumpL || s->dumpMulti || count || ntiles < 2 || multi) ? 1u : (uint32_t)s->lanes;
-    const uint32_t lanePaths = std::max<uint32_t>(TILE * TILE, maxPaths / nl);
-    const uint32_t sppPerBatch = std::max(1u, std::min(p->spp, lanePaths / (TILE * TILE)));
-    // equal-sized batches, a multiple of the lane count: a nearly empty last
-    // batch costs a full set of bounce launches (and their tails) for a
-    // sliver of the work
-    const uint32_t tilesMax = std::max(1u, lanePaths / (TILE * TILE * sppPerBatch));
-    uint32_t nTileBatches = std::max(1u, (ntiles + tilesMax - 1) / tilesMax);
-    nTileBatches = std::min(ntiles ? ntiles : 1u, (nTileBatches + nl - 1) / nl * nl);
-    const uint32_t tilesPerBatch = std::max(1u, (ntiles + nTileBatches - 1) / nTileBatches);
-    if ((rc = ensure_batch(s, tilesPerBatch * sppPerBatch * TILE * TILE, (int)nl)) != MTSG_OK) return rc;
-    const bool fieldsOnly = multi && s->aov.pathChild < 0;
-    if (multi) {
-        if ((rc = ensure_fields(s)) != MTSG_OK) return rc;
-        s->aov.planes = s->fieldPlanes;
-        s->aov.cap = s->fieldCap;
-    }
-    const int blockW = p->tile_w + 2 * s->cam.border, blockH = p->tile_h + 2 * s->cam.border;
-    DevIntegrator I{p->max_depth, p->rr_depth, p->strict_normals, p->hide_emitters, p->spp, p->seed, (uint32_t)s->cam.film_w,
-                    make_sampler(s, p->spp)};
-    I.om = p->integrator == MTSG_INTEGRATOR_PATH2_OM ? 1 : 0;
-    I.om_strategy = p->om_strategy;
-    I.om_mis = p->om_mis;
-    I.om_jitter = p->om_jitter;
-    memset(&s->stats, 0, sizeof(s->stats));
-    s->wtLaunches = 0;
-    if ((s->flags & MTSG_FLAG_WAVETIME) && !s->waveTimes)
-        HIP_TRY(hipMalloc((void **)&s->waveTimes, (size_t)WT_WORDS * s->traceGrid * WT_MAX_LAUNCHES * sizeof(unsigned long long)));
-    s->evUsed = 0;
-    s->timed.clear();
-    // the cancel flag is consumed (cleared) when a render returns, so a
-    // cancel that races with the start of a render is not lost
-    if (count) HIP_TRY(hipMemsetAsync(s->LP[0].ctr, 0, CTR_WORDS * sizeof(unsigned long long), s->stream));
-    // row rotation of the tile deal (include/mtsg.h): fixed at 1, as the
-    // oracle, mtsg_tile_windows and mtsg.put_tile_windows assume (the round-3
-    // measurement override is gone: a rank with another rotation would put
-    // its tiles in the wrong places without an error)
-    const int dealSkew = 1;
-    // the batches of this call, tile-major
-    std::vector<DevBatch> batches;
-    for (uint32_t t0i = 0; t0i < ntiles; t0i += tilesPerBatch) {
-        for (uint32_t s0 = 0; s0 < p->spp; s0 += sppPerBatch) {
-            DevBatch B;
-            B.rect_x = p->tile_x; B.rect_y = p->tile_y; B.rect_w = p->tile_w; B.rect_h = p->tile_h;
-            B.tiles_x = (int)tilesX;
-            B.skew = dealSkew;
-            B.tile0 = (int)t0i;
-            B.tstride = (int)tstride;
-            B.toffset = (int)toffset;
-            B.ntiles = (int)std::min(tilesPerBatch, ntiles - t0i);
-            B.s0 = s0;
-            B.ns = std::min(sppPerBatch, p->spp - s0);
-            B.nslots = (uint32_t)B.ntiles * B.ns * TILE * TILE;
-            B.keys = listed ? s->tileKeysDev : nullptr;
-            batches.push_back(B);
-        }
-    }
-    struct LaneRun {
+struct RenderRun {
+    mtsg_scene *s;
+    const mtsg_render_params *p;
+    DevIntegrator I;
+    RenderPlan plan;
+    float *film;
+    int win;
+    bool multi;
+    std::chrono::steady_clock::time_point t0;
+    bool count = false;
+    bool fieldsOnly = false;   // multichannel without a `path` child
+    bool useFinish = false;    // tail mode (k_finish)
+    int blockW = 0, blockH = 0, maxBounces = 0;
+    struct Lane {
         DevBatch B;
         int last = -1;
         int start = 0;
         bool open = false;
         bool finished = false;   // the tail kernel took over the batch's remaining bounces
         hipEvent_t cntEv[2] = {nullptr, nullptr};
-    } lr[MTSG_MAX_LANES];
-    int result = MTSG_OK;
-    for (uint32_t l = 0; l < nl && result == MTSG_OK; ++l)
-        for (int k = 0; k < 2; ++k)
-            if (hipEventCreateWithFlags(&lr[l].cntEv[k], hipEventDisableTiming) != hipSuccess) { g_err = "event"; result = MTSG_ERR_DEVICE; }
-    // work the caller queued on s->stream (the film memset of mtsg_render)
-    // precedes every lane's first kernel
+    } lane[MTSG_MAX_LANES];
     hipEvent_t startEv = nullptr;
-    if (result == MTSG_OK && nl > 1) {
-        if (hipEventCreateWithFlags(&startEv, hipEventDisableTiming) != hipSuccess || hipEventRecord(startEv, s->stream) != hipSuccess) {
-            g_err = "event";
-            result = MTSG_ERR_DEVICE;
-        }
-        for (uint32_t l = 1; l < nl && result == MTSG_OK; ++l)
-            if (hipStreamWaitEvent(s->lstream[l], startEv, 0) != hipSuccess) { g_err = "stream wait"; result = MTSG_ERR_DEVICE; }
-    }
-    // myPath2_OM shades depths 1..maxDepthEye and one more launch books the
-    // emitters its last BSDF rays found
-    const int maxBounces = I.om ? p->max_depth + 1 : (p->max_depth > 0 ? p->max_depth : 1 << 30);
-    // tail mode (k_finish): one lane, not in the instrumented or myPath2_OM modes
-    const bool useFinish = s->finishPaths > 0 && nl == 1 && !count && !I.om && !s->knobs;
-    // bounce b of a lane: one trace launch over this bounce's closest rays
-    // (work list qin(b), identity for b = 0) and bounce b-1's shadow rays
-    // (S((b-1) & 1)), then k_shade appends the next bounce's paths to
-    // qout(b) = (b & 1) ^ 1 and its shadow rays to S(b & 1)
-    auto hostCnt = [&](uint32_t l, int bb) { return s->hostCnt + HOSTCNT_STRIDE * (2 * l + (bb & 1)); };
-    auto account = [&](uint32_t l, int bb) {
+
+    // the deal key of virtual tile v, on the host
+    int hostKey(int v) const { return s->tileKeys.empty() ? (int)plan.toffset + v * (int)plan.tstride : s->tileKeys[v]; }
+    uint32_t *hostCnt(uint32_t l, int bb) const { return s->hostCnt + HOSTCNT_STRIDE * (2 * l + (bb & 1)); }
+    // books bounce bb of lane l from its counters' copy; returns the paths it left for bounce bb + 1
+    uint32_t account(uint32_t l, int bb) {
         const uint32_t *hc = hostCnt(l, bb);
-        const uint32_t consumed = bb == 0 ? lr[l].B.nslots : hc[(bb & 1) ? CNT_Q1 : CNT_Q0];
+        const uint32_t consumed = bb == 0 ? lane[l].B.nslots : hc[(bb & 1) ? CNT_Q1 : CNT_Q0];
         s->stats.rays_closest += consumed;
         s->stats.rays_shadow += hc[cnt_s(bb & 1)];
         s->stats.launches_trace_closest++;
         return hc[((bb & 1) ^ 1) ? CNT_Q1 : CNT_Q0];
-    };
-    // every error inside the batch loop returns from `run`; the lanes are then
-    // drained and the per-render events destroyed below, whatever happened
-    auto run = [&]() -> int {
-    for (size_t k0 = 0; k0 < batches.size(); k0 += nl) {
-        if (s->cancel.load()) { g_err = "cancelled"; return MTSG_ERR_CANCELLED; }
-        const uint32_t nb = (uint32_t)std::min<size_t>(nl, batches.size() - k0);
-        for (uint32_t l = 0; l < nb; ++l) {
-            LaneRun &L = lr[l];
-            L.B = batches[k0 + l];
-            L.last = -1;
-            L.open = true;
-            L.finished = false;
-            // staggered lanes: lane l starts `stagger` bounces after lane
-            // l-1, so its early, full launches overlap the other lanes'
-            // late, tail-bound ones
-            L.start = (int)l * s->stagger;
+    }
+    DevBatch dev_batch(const PlanBatch &b) const {   // (in DevBatch's field order)
+        return DevBatch{p->tile_x, p->tile_y, p->tile_w, p->tile_h, (int)plan.tilesX, (int)b.tile0, (int)b.ntiles,
+                        (int)plan.tstride, (int)plan.toffset, PLAN_DEAL_SKEW, b.s0, b.ns, b.nslots,
+                        s->tileKeys.empty() ? nullptr : s->tileKeysDev};
+    }
+    FieldsLaunch fields(uint32_t l) const {
+        return FieldsLaunch{s->lstream[l], &s->ds, &s->cam, &I, &lane[l].B, &s->LP[l], &s->aov, film, blockW, blockH, win};
+    }
+    // the rectangle's part of tile v: origin and size
+    void tile_rect(int key, const DevBatch &B, int &x, int &y, int &w, int &h) const {
+        int tx, ty;
+        tile_of_key(key, B.tiles_x, tx, ty, B.skew);
+        x = tx * TILE;
+        y = ty * TILE;
+        w = std::min(TILE, p->tile_w - x);
+        h = std::min(TILE, p->tile_h - y);
+    }
+
+    // the per-render events; work the caller queued on s->stream (the film
+    // memset of mtsg_render) precedes every lane's first kernel
+    int open_lanes() {
+        for (uint32_t l = 0; l < plan.lanes; ++l)
+            for (int k = 0; k < 2; ++k)
+                if (hipEventCreateWithFlags(&lane[l].cntEv[k], hipEventDisableTiming) != hipSuccess) { g_err = "event"; return MTSG_ERR_DEVICE; }
+        if (plan.lanes > 1) {
+            if (hipEventCreateWithFlags(&startEv, hipEventDisableTiming) != hipSuccess || hipEventRecord(startEv, s->stream) != hipSuccess) {
+                g_err = "event";
+                return MTSG_ERR_DEVICE;
+            }
+            for (uint32_t l = 1; l < plan.lanes; ++l)
+                if (hipStreamWaitEvent(s->lstream[l], startEv, 0) != hipSuccess) { g_err = "stream wait"; return MTSG_ERR_DEVICE; }
         }
-        for (int gb = 0;; ++gb) {
-            // cancel() between bounces (the whole frame is usually one batch)
-            if (s->cancel.load()) { g_err = "cancelled"; return MTSG_ERR_CANCELLED; }
-            bool any = false;
-            for (uint32_t l = 0; l < nb; ++l) {
-                LaneRun &L = lr[l];
-                if (!L.open) continue;
-                const int b = gb - L.start;
-                if (b < 0) continue;
-                DevPaths &P = s->LP[l];
-                hipStream_t st = s->lstream[l];
-                if (b == 0) {
-                    HIP_TRY(hipMemsetAsync(P.cnt, 0, CNT_WORDS * sizeof(uint32_t), st));
-                    timed_launch(s, K_CAMERA, st, [&]() {
-                        hipLaunchKernelGGL(k_camera, dim3((L.B.nslots + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, s->cam, I, L.B, P);
-                    });
-                }
-                const int qin = b == 0 ? -1 : (b & 1);
-                const int qout = (b & 1) ^ 1;
-                hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, st, P.cnt, qout, b & 1);
-                // bounce rays in direction-sorted windows (k_sortwin); the
-                // camera rays keep their tile order
-                DevPaths PT = P;
-                PT.camEnc = (b == 0 && s->ds.camCompact) ? 1u : 0u;   // bounce 0: camera rays as k_camera stores them
-                if (b >= 1 && s->rayOrder == 1) {
-                    timed_launch(s, K_SORT, st, [&]() {
-                        hipLaunchKernelGGL(k_sortwin, dim3(s->cuCount * 2), dim3(SORT_BLOCK), 0, st, P, qin);
-                    });
-                    PT.order = P.orderBuf;
-                }
-                timed_launch(s, K_CLOSEST, st, [&]() { launch_trace(s, count, PT, qin, b == 0 ? -1 : ((b - 1) & 1), L.B.nslots, st); });
-                if (multi && b == 0) {
-                    // the bounce-0 hits are final (the tie retrace is part of the trace
-                    // launch) and the work list is the identity: the field children
-                    if (s->aov.nf || fieldsOnly) launch_fields(fields_args(s, I, L.B, P, st, film, blockW, blockH, win));
-                    if (fieldsOnly) {
-                        // no `path` child: no shading, no further bounce; the counters'
-                        // copy carries the traversal's error word
-                        HIP_TRY(hipMemcpyAsync(hostCnt(l, 0), P.cnt, (CNT_S1 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                        HIP_TRY(hipEventRecord(L.cntEv[0], st));
-                        L.last = 0;
-                        L.open = false;
-                        L.finished = true;
-                        continue;
-                    }
-                }
-                if (useFinish && b >= 1) {
-                    // the count of this bounce's paths is known once bounce b-1 is
-                    // done (the GPU meanwhile runs this bounce's trace): few left ->
-                    // k_finish carries them to their ends in one launch
-                    HIP_TRY(hipEventSynchronize(L.cntEv[(b - 1) & 1]));
-                    const uint32_t nb = account(l, b - 1);
-                    if (nb < s->finishPaths) {
-                        hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, st, P.cnt, -1, -1);
-                        timed_launch(s, K_FINISH, st, [&]() { launch_finish(s, I, L.B, P, qin, st); });
-                        s->stats.launches_finish++;
-                        s->stats.paths_finish += nb;
-                        HIP_TRY(hipMemcpyAsync(hostCnt(l, b), P.cnt, (CNT_S1 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                        HIP_TRY(hipEventRecord(L.cntEv[b & 1], st));
-                        L.last = b;
-                        L.open = false;
-                        L.finished = true;
-                        continue;
-                    }
-                }
-                timed_launch(s, K_SHADE, st, [&]() { launch_shade(s, I, L.B, P, b, qin, st); });
-                swap_bounce(P);
-                HIP_TRY(hipMemcpyAsync(hostCnt(l, b), P.cnt, (CNT_S1 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(L.cntEv[b & 1], st));
-                L.last = b;
-                if (b + 1 >= maxBounces) L.open = false;
-            }
-            for (uint32_t l = 0; l < nb; ++l) {
-                LaneRun &L = lr[l];
-                const int b = gb - L.start;
-                // lagged check: if bounce b-1 produced nothing, bounce b was empty
-                // (also for a lane that launched its last bounce b just now, so
-                // every bounce is booked once: b-1 here, the last one below)
-                if (b >= 1 && L.last == b && !useFinish) {
-                    HIP_TRY(hipEventSynchronize(L.cntEv[(b - 1) & 1]));
-                    if (account(l, b - 1) == 0) L.open = false;
-                }
-                any |= L.open;
-            }
-            if (!any) break;
-        }
-        for (uint32_t l = 0; l < nb; ++l) {
-            LaneRun &L = lr[l];
-            DevPaths &P = s->LP[l];
-            hipStream_t st = s->lstream[l];
-            const DevBatch &B = L.B;
-            if (L.last >= 0 && !L.finished) {
-                // the last bounce's shadow rays
-                hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, st, P.cnt, -1, -1);
-                timed_launch(s, K_SHADOW, st, [&]() { launch_trace(s, count, P, -2, L.last & 1, 0u, st); });
-                s->stats.launches_trace_shadow++;
-                // the error word again, after this launch: a traversal error of
-                // the last bounce's shadow rays fails the render too (the copy
-                // of bounce L.last's counters was taken before this launch)
-                HIP_TRY(hipMemcpyAsync(hostCnt(l, L.last) + CNT_ERR, P.cnt + CNT_ERR, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(L.cntEv[L.last & 1], st));
-            }
-            if (multi) timed_launch(s, K_SPLAT, st, [&]() { launch_splat_multi(fields_args(s, I, B, P, st, film, blockW, blockH, win)); });
-            else timed_launch(s, K_SPLAT, st, [&]() {
-                dim3 g(B.ntiles, (B.ns + SPLAT_CHUNK - 1) / SPLAT_CHUNK);
-                const int K = 2 * s->cam.border + 1;
-                if (K == 5 && !s->cam.has_alpha) hipLaunchKernelGGL((k_splat<5, 4>), g, dim3(BLOCK), 0, st, s->cam, I, B, P, film, blockW, blockH, win);
-                else if (K == 5) hipLaunchKernelGGL((k_splat<5, 5>), g, dim3(BLOCK), 0, st, s->cam, I, B, P, film, blockW, blockH, win);
-                else if (K <= 3 && !s->cam.has_alpha) hipLaunchKernelGGL((k_splat<3, 4>), g, dim3(BLOCK), 0, st, s->cam, I, B, P, film, blockW, blockH, win);
-                else if (K <= 3) hipLaunchKernelGGL((k_splat<3, 5>), g, dim3(BLOCK), 0, st, s->cam, I, B, P, film, blockW, blockH, win);
-                else if (!s->cam.has_alpha) hipLaunchKernelGGL((k_splat<9, 4>), g, dim3(BLOCK), 0, st, s->cam, I, B, P, film, blockW, blockH, win);
-                else hipLaunchKernelGGL((k_splat<9, 5>), g, dim3(BLOCK), 0, st, s->cam, I, B, P, film, blockW, blockH, win);
+        return MTSG_OK;
+    }
+
+    // the copy of a bounce's queue counters that account() and the error check read
+    int copy_counters(uint32_t l, int b) {
+        HIP_TRY(hipMemcpyAsync(hostCnt(l, b), s->LP[l].cnt, (CNT_S1 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->lstream[l]));
+        HIP_TRY(hipEventRecord(lane[l].cntEv[b & 1], s->lstream[l]));
+        lane[l].last = b;
+        return MTSG_OK;
+    }
+    // the batch needs no further bounce launches
+    int end_lane(uint32_t l, int b) {
+        lane[l].open = false;
+        lane[l].finished = true;
+        return copy_counters(l, b);
+    }
+
+    // issue bounce b of lane l: camera, reset, optional sort, trace, fields,
+    // then the tail kernel or shade, then the counters' copy
+    int issue_bounce(uint32_t l, int b) {
+        Lane &L = lane[l];
+        DevPaths &P = s->LP[l];
+        hipStream_t st = s->lstream[l];
+        if (b == 0) {
+            HIP_TRY(hipMemsetAsync(P.cnt, 0, CNT_WORDS * sizeof(uint32_t), st));
+            timed_launch(s, K_CAMERA, st, [&]() {
+                hipLaunchKernelGGL(k_camera, dim3((L.B.nslots + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, s->cam, I, L.B, P);
             });
-            s->stats.samples += (uint64_t)B.nslots;
         }
+        const int qin = b == 0 ? -1 : (b & 1);
+        const int qout = (b & 1) ^ 1;
+        hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, st, P.cnt, qout, b & 1);
+        // bounce rays in direction-sorted windows (k_sortwin); the
+        // camera rays keep their tile order
+        DevPaths PT = P;
+        PT.camEnc = (b == 0 && s->ds.camCompact) ? 1u : 0u;   // bounce 0: camera rays as k_camera stores them
+        if (b >= 1 && s->rayOrder == 1) {
+            timed_launch(s, K_SORT, st, [&]() {
+                hipLaunchKernelGGL(k_sortwin, dim3(s->cuCount * 2), dim3(SORT_BLOCK), 0, st, P, qin);
+            });
+            PT.order = P.orderBuf;
+        }
+        timed_launch(s, K_CLOSEST, st, [&]() { launch_trace(s, count, PT, qin, b == 0 ? -1 : ((b - 1) & 1), L.B.nslots, st); });
+        if (multi && b == 0) {
+            // the bounce-0 hits are final (the tie retrace is part of the trace
+            // launch) and the work list is the identity: the field children
+            if (s->aov.nf || fieldsOnly) launch_fields(fields(l));
+            // no `path` child: no shading, no further bounce; the counters'
+            // copy carries the traversal's error word
+            if (fieldsOnly) return end_lane(l, 0);
+        }
+        if (useFinish && b >= 1) {
+            // the count of this bounce's paths is known once bounce b-1 is
+            // done (the GPU meanwhile runs this bounce's trace): few left ->
+            // k_finish carries them to their ends in one launch
+            HIP_TRY(hipEventSynchronize(L.cntEv[(b - 1) & 1]));
+            const uint32_t left = account(l, b - 1);
+            if (left < s->finishPaths) {
+                hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, st, P.cnt, -1, -1);
+                timed_launch(s, K_FINISH, st, [&]() { launch_finish(s, I, L.B, P, qin, st); });
+                s->stats.launches_finish++;
+                s->stats.paths_finish += left;
+                return end_lane(l, b);
+            }
+        }
+        timed_launch(s, K_SHADE, st, [&]() { launch_shade(s, I, L.B, P, b, qin, st); });
+        swap_bounce(P);
+        if (b + 1 >= maxBounces) L.open = false;
+        return copy_counters(l, b);
+    }
+
+    // lagged check: if bounce b-1 produced nothing, bounce b was empty
+    // (also for a lane that launched its last bounce b just now, so
+    // every bounce is booked once: b-1 here, the last one in collect_batch)
+    int check_empty(uint32_t l, int b) {
+        Lane &L = lane[l];
+        if (b >= 1 && L.last == b && !useFinish) {
+            HIP_TRY(hipEventSynchronize(L.cntEv[(b - 1) & 1]));
+            if (account(l, b - 1) == 0) L.open = false;
+        }
+        return MTSG_OK;
+    }
+
+    // close lane l's batch: the last bounce's shadow rays, then the splat
+    int close_batch(uint32_t l) {
+        Lane &L = lane[l];
+        DevPaths &P = s->LP[l];
+        hipStream_t st = s->lstream[l];
+        if (L.last >= 0 && !L.finished) {
+            hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, st, P.cnt, -1, -1);
+            timed_launch(s, K_SHADOW, st, [&]() { launch_trace(s, count, P, -2, L.last & 1, 0u, st); });
+            s->stats.launches_trace_shadow++;
+            // the error word again, after this launch: a traversal error of
+            // the last bounce's shadow rays fails the render too (the copy
+            // of bounce L.last's counters was taken before this launch)
+            HIP_TRY(hipMemcpyAsync(hostCnt(l, L.last) + CNT_ERR, P.cnt + CNT_ERR, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(L.cntEv[L.last & 1], st));
+        }
+        timed_launch(s, K_SPLAT, st, [&]() {
+            if (multi) launch_splat_multi(fields(l));
+            else launch_splat(s, I, L.B, P, film, blockW, blockH, win, st);
+        });
+        s->stats.samples += (uint64_t)L.B.nslots;
+        return MTSG_OK;
+    }
+
+    // collect the nb batches in flight: the last bounce's accounting and the
+    // error word, then the tile callbacks and the debug dumps
+    int collect_batches(uint32_t nb) {
         for (uint32_t l = 0; l < nb; ++l) {
-            LaneRun &L = lr[l];
+            Lane &L = lane[l];
             if (L.last < 0) continue;
             HIP_TRY(hipEventSynchronize(L.cntEv[L.last & 1]));
             if (fieldsOnly) {
                 // one closest launch per batch, one camera ray per sample inside the rectangle
                 s->stats.launches_trace_closest++;
                 for (int tl = 0; tl < L.B.ntiles; ++tl) {
-                    int tx, ty;
-                    tile_of_key(hostKey(L.B.tile0 + tl), L.B.tiles_x, tx, ty, L.B.skew);
-                    s->stats.rays_closest += (uint64_t)std::min(TILE, p->tile_w - tx * TILE) * std::min(TILE, p->tile_h - ty * TILE) * L.B.ns;
+                    int x, y, w, h;
+                    tile_rect(hostKey(L.B.tile0 + tl), L.B, x, y, w, h);
+                    s->stats.rays_closest += (uint64_t)w * h * L.B.ns;
                 }
             } else {
                 account(l, L.last);
@@ -734,140 +695,265 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
             // the tiles whose last samples this batch splatted are complete
             for (uint32_t l = 0; l < nb; ++l) {
                 HIP_TRY(hipStreamSynchronize(s->lstream[l]));
-                const DevBatch &B = lr[l].B;
+                const DevBatch &B = lane[l].B;
                 if (B.s0 + B.ns < p->spp) continue;
                 for (int tl = 0; tl < B.ntiles; ++tl) {
                     const int key = hostKey(B.tile0 + tl);
-                    int tx, ty;
-                    tile_of_key(key, B.tiles_x, tx, ty, B.skew);
-                    const int x = tx * TILE, y = ty * TILE;
-                    s->tileFn(s->tileUser, key, p->tile_x + x, p->tile_y + y, std::min(TILE, p->tile_w - x),
-                              std::min(TILE, p->tile_h - y));
+                    int x, y, w, h;
+                    tile_rect(key, B, x, y, w, h);
+                    s->tileFn(s->tileUser, key, p->tile_x + x, p->tile_y + y, w, h);
                 }
             }
         }
-        if (s->dumpMulti) {
-            // debug: the batch's per-slot children (single batch, one lane): the
-            // `path` child and alpha from L, the fields from their planes
-            const DevBatch &B = lr[0].B;
-            const DevAov &A = s->aov;
-            std::vector<float4> L(B.nslots);
-            std::vector<float> F((size_t)3 * A.nf * B.nslots);
-            HIP_TRY(hipMemcpyAsync(L.data(), s->LP[0].L, B.nslots * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
-            for (int k = 0; k < 3 * A.nf; ++k)
-                HIP_TRY(hipMemcpyAsync(F.data() + (size_t)k * B.nslots, A.planes + (size_t)k * A.cap, B.nslots * sizeof(float),
-                                       hipMemcpyDeviceToHost, s->stream));
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            const size_t per = (size_t)3 * A.m + 1;
-            for (uint32_t slot = 0; slot < B.nslots; ++slot) {
-                const uint32_t pix = slot & (TILE * TILE - 1), rest = slot >> 8;
-                const uint32_t sl = rest % B.ns, tl = rest / B.ns;
-                int tx, ty;
-                tile_of_key(hostKey(B.tile0 + (int)tl), B.tiles_x, tx, ty, B.skew);
-                int lx, ly;
-                tile_pix(pix, lx, ly);
-                const int x = tx * TILE + lx, y = ty * TILE + ly;
-                if (x >= p->tile_w || y >= p->tile_h) continue;
-                float *o = s->dumpMulti + (((size_t)y * p->tile_w + x) * p->spp + B.s0 + sl) * per;
-                if (A.pathChild >= 0) { o[3 * A.pathChild] = L[slot].x; o[3 * A.pathChild + 1] = L[slot].y; o[3 * A.pathChild + 2] = L[slot].z; }
-                for (int f = 0; f < A.nf; ++f)
-                    for (int c = 0; c < 3; ++c) o[3 * A.child[f] + c] = F[(size_t)(3 * f + c) * B.nslots + slot];
-                o[3 * A.m] = L[slot].w;
-            }
-        }
-        if (s->dumpL) {
-            // debug: copy the batch's per-slot radiance (single batch, one lane)
-            const DevBatch &B = lr[0].B;
-            std::vector<float4> L(B.nslots);
-            HIP_TRY(hipMemcpyAsync(L.data(), s->LP[0].L, B.nslots * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            for (uint32_t slot = 0; slot < B.nslots; ++slot) {
-                const uint32_t pix = slot & (TILE * TILE - 1), rest = slot >> 8;
-                const uint32_t sl = rest % B.ns, tl = rest / B.ns;
-                int tx, ty;
-                tile_of_key(hostKey(B.tile0 + (int)tl), B.tiles_x, tx, ty, B.skew);
-                int lx, ly;
-                tile_pix(pix, lx, ly);
-                const int x = tx * TILE + lx, y = ty * TILE + ly;
-                if (x >= p->tile_w || y >= p->tile_h) continue;
-                float *o = s->dumpL + (((size_t)y * p->tile_w + x) * p->spp + B.s0 + sl) * 4;
-                o[0] = L[slot].x; o[1] = L[slot].y; o[2] = L[slot].z; o[3] = L[slot].w;
-            }
+        int rc = MTSG_OK;
+        if (s->dumpMulti) rc = dump_multi();
+        if (rc == MTSG_OK && s->dumpL) rc = dump_radiance();
+        return rc;
+    }
+
+    // debug dumps (single batch, one lane): f(slot, i) for every slot of the
+    // batch inside the rectangle, i the index of its sample in [tile_h][tile_w][spp]
+    template <class F>
+    void for_each_sample(F f) const {
+        const DevBatch &B = lane[0].B;
+        for (uint32_t slot = 0; slot < B.nslots; ++slot) {
+            const uint32_t pix = slot & (TILE * TILE - 1), rest = slot >> 8;
+            const uint32_t sl = rest % B.ns, tl = rest / B.ns;
+            int tx, ty;
+            tile_of_key(hostKey(B.tile0 + (int)tl), B.tiles_x, tx, ty, B.skew);
+            int lx, ly;
+            tile_pix(pix, lx, ly);
+            const int x = tx * TILE + lx, y = ty * TILE + ly;
+            if (x >= p->tile_w || y >= p->tile_h) continue;
+            f(slot, ((size_t)y * p->tile_w + x) * p->spp + B.s0 + sl);
         }
     }
-    return MTSG_OK;
-    };
-    if (result == MTSG_OK) result = run();
+    // the batch's per-slot children: the `path` child and alpha from L, the
+    // fields from their planes
+    int dump_multi() const {
+        const uint32_t n = lane[0].B.nslots;
+        const DevAov &A = s->aov;
+        std::vector<float4> L(n);
+        std::vector<float> F((size_t)3 * A.nf * n);
+        HIP_TRY(hipMemcpyAsync(L.data(), s->LP[0].L, n * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
+        for (int k = 0; k < 3 * A.nf; ++k)
+            HIP_TRY(hipMemcpyAsync(F.data() + (size_t)k * n, A.planes + (size_t)k * A.cap, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        const size_t per = (size_t)3 * A.m + 1;
+        for_each_sample([&](uint32_t slot, size_t i) {
+            float *o = s->dumpMulti + i * per;
+            if (A.pathChild >= 0) { o[3 * A.pathChild] = L[slot].x; o[3 * A.pathChild + 1] = L[slot].y; o[3 * A.pathChild + 2] = L[slot].z; }
+            for (int f = 0; f < A.nf; ++f)
+                for (int c = 0; c < 3; ++c) o[3 * A.child[f] + c] = F[(size_t)(3 * f + c) * n + slot];
+            o[3 * A.m] = L[slot].w;
+        });
+        return MTSG_OK;
+    }
+    // the batch's per-slot radiance
+    int dump_radiance() const {
+        const uint32_t n = lane[0].B.nslots;
+        std::vector<float4> L(n);
+        HIP_TRY(hipMemcpyAsync(L.data(), s->LP[0].L, n * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        for_each_sample([&](uint32_t slot, size_t i) {
+            float *o = s->dumpL + i * 4;
+            o[0] = L[slot].x; o[1] = L[slot].y; o[2] = L[slot].z; o[3] = L[slot].w;
+        });
+        return MTSG_OK;
+    }
+
+    // every error in here returns at once; finish() then drains the lanes
+    // and destroys the per-render events, whatever happened
+    int run_batches() {
+        const uint32_t nl = plan.lanes;
+        for (size_t k0 = 0; k0 < plan.batches.size(); k0 += nl) {
+            if (s->cancel.load()) { g_err = "cancelled"; return MTSG_ERR_CANCELLED; }
+            const uint32_t nb = (uint32_t)std::min<size_t>(nl, plan.batches.size() - k0);
+            for (uint32_t l = 0; l < nb; ++l) {
+                Lane &L = lane[l];
+                L.B = dev_batch(plan.batches[k0 + l]);
+                L.last = -1;
+                L.open = true;
+                L.finished = false;
+                // staggered lanes: lane l starts `stagger` bounces after lane
+                // l-1, so its early, full launches overlap the other lanes'
+                // late, tail-bound ones
+                L.start = (int)l * s->stagger;
+            }
+            int rc;
+            for (int gb = 0;; ++gb) {
+                // cancel() between bounces (the whole frame is usually one batch)
+                if (s->cancel.load()) { g_err = "cancelled"; return MTSG_ERR_CANCELLED; }
+                for (uint32_t l = 0; l < nb; ++l)
+                    if (lane[l].open && gb >= lane[l].start && (rc = issue_bounce(l, gb - lane[l].start)) != MTSG_OK) return rc;
+                bool any = false;
+                for (uint32_t l = 0; l < nb; ++l) {
+                    if ((rc = check_empty(l, gb - lane[l].start)) != MTSG_OK) return rc;
+                    any |= lane[l].open;
+                }
+                if (!any) break;
+            }
+            for (uint32_t l = 0; l < nb; ++l)
+                if ((rc = close_batch(l)) != MTSG_OK) return rc;
+            if ((rc = collect_batches(nb)) != MTSG_OK) return rc;
+        }
+        return MTSG_OK;
+    }
+
     // drain every lane (also after an error or a cancel: the caller may free
-    // the film as soon as this returns) and release the per-render events
-    hipError_t e = hipSuccess;
-    for (uint32_t l = 0; l < nl; ++l) {
-        const hipError_t el = hipStreamSynchronize(s->lstream[l]);
-        if (e == hipSuccess) e = el;
-        for (int k = 0; k < 2; ++k)
-            if (lr[l].cntEv[k]) hipEventDestroy(lr[l].cntEv[k]);
-    }
-    if (startEv) hipEventDestroy(startEv);
-    s->cancel.store(0);
-    if (e != hipSuccess) { g_err = std::string("render: ") + hipGetErrorString(e); return MTSG_ERR_DEVICE; }
-    e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("kernel launch: ") + hipGetErrorString(e); return MTSG_ERR_DEVICE; }
-    if (result != MTSG_OK) return result;
-    // samples actually inside the rectangle (all tiles of this call)
-    if (tstride == 1 && !listed) s->stats.samples = (uint64_t)p->tile_w * p->tile_h * p->spp;
-    if (s->flags & MTSG_FLAG_TIMING) {
-        for (auto &te : s->timed) {
-            float ms = 0;
-            hipEventElapsedTime(&ms, s->evPool[te.second], s->evPool[te.second + 1]);
-            switch (te.first) {
-                case K_CAMERA: s->stats.ms_camera += ms; break;
-                case K_CLOSEST: s->stats.ms_trace_closest += ms; break;
-                case K_SHADOW: s->stats.ms_trace_shadow += ms; break;
-                case K_SHADE: s->stats.ms_shade += ms; break;
-                case K_SPLAT: s->stats.ms_splat += ms; break;
-                case K_FINISH: s->stats.ms_finish += ms; break;
-                case K_SORT: s->stats.ms_sort += ms; break;
+    // the film as soon as this returns), release the per-render events and
+    // consume the cancel flag; then the timings and counters of a good render
+    int finish(int result) {
+        hipError_t e = hipSuccess;
+        for (uint32_t l = 0; l < plan.lanes; ++l) {
+            const hipError_t el = hipStreamSynchronize(s->lstream[l]);
+            if (e == hipSuccess) e = el;
+            for (int k = 0; k < 2; ++k)
+                if (lane[l].cntEv[k]) hipEventDestroy(lane[l].cntEv[k]);
+        }
+        if (startEv) hipEventDestroy(startEv);
+        // the cancel flag is consumed (cleared) when a render returns, so a
+        // cancel that races with the start of a render is not lost
+        s->cancel.store(0);
+        if (e != hipSuccess) { g_err = std::string("render: ") + hipGetErrorString(e); return MTSG_ERR_DEVICE; }
+        e = hipGetLastError();
+        if (e != hipSuccess) { g_err = std::string("kernel launch: ") + hipGetErrorString(e); return MTSG_ERR_DEVICE; }
+        if (result != MTSG_OK) return result;
+        mtsg_stats &st = s->stats;
+        // samples actually inside the rectangle (all tiles of this call)
+        if (plan.tstride == 1 && s->tileKeys.empty()) st.samples = (uint64_t)p->tile_w * p->tile_h * p->spp;
+        if (s->flags & MTSG_FLAG_TIMING) {
+            // in the order of K_CAMERA .. K_SORT
+            double *const sums[] = {&st.ms_camera, &st.ms_trace_closest, &st.ms_trace_shadow, &st.ms_shade, &st.ms_splat, &st.ms_finish, &st.ms_sort};
+            for (auto &te : s->timed) {
+                float ms = 0;
+                hipEventElapsedTime(&ms, s->evPool[te.second], s->evPool[te.second + 1]);
+                *sums[te.first] += ms;
             }
         }
-    }
-    if (count) {
-        unsigned long long c[CTR_WORDS];
-        HIP_TRY(hipMemcpy(c, s->LP[0].ctr, sizeof(c), hipMemcpyDeviceToHost));
-        s->stats.nodes_visited = c[0];
-        s->stats.leaf_refs = c[1];
-        s->stats.tri_tests = c[2];
-        s->stats.wave_node_iters = c[3];
-        s->stats.wave_test_iters = c[4];
-        s->stats.wave_steps = c[5];
-        s->stats.wave_active_lanes = c[6];
-        s->stats.shadow_nodes_visited = c[8];
-        s->stats.shadow_leaf_refs = c[9];
-        s->stats.shadow_tri_tests = c[10];
-        s->stats.shadow_wave_node_iters = c[11];
-        s->stats.shadow_wave_test_iters = c[12];
-        s->stats.shadow_wave_steps = c[13];
-        s->stats.shadow_wave_active_lanes = c[14];
-        s->stats.iter_max_closest = c[7];
-        s->stats.iter_max_shadow = c[15];
-        for (int k = 0; k < 16; ++k) {
-            s->stats.iter_hist_closest[k] = c[16 + k];
-            s->stats.iter_hist_shadow[k] = c[32 + k];
+        if (count) {
+            // the traversal counters, by the names of kernels.h (CTR_*)
+            unsigned long long c[CTR_WORDS];
+            HIP_TRY(hipMemcpy(c, s->LP[0].ctr, sizeof(c), hipMemcpyDeviceToHost));
+            const unsigned long long *sh = c + CTR_SHADOW;
+            st.nodes_visited = c[CTR_NODES];                     st.shadow_nodes_visited = sh[CTR_NODES];
+            st.leaf_refs = c[CTR_REFS];                          st.shadow_leaf_refs = sh[CTR_REFS];
+            st.tri_tests = c[CTR_TESTS];                         st.shadow_tri_tests = sh[CTR_TESTS];
+            st.wave_node_iters = c[CTR_WAVE_NODE_ITERS];         st.shadow_wave_node_iters = sh[CTR_WAVE_NODE_ITERS];
+            st.wave_test_iters = c[CTR_WAVE_TEST_ITERS];         st.shadow_wave_test_iters = sh[CTR_WAVE_TEST_ITERS];
+            st.wave_steps = c[CTR_WAVE_STEPS];                   st.shadow_wave_steps = sh[CTR_WAVE_STEPS];
+            st.wave_active_lanes = c[CTR_WAVE_ACTIVE];           st.shadow_wave_active_lanes = sh[CTR_WAVE_ACTIVE];
+            st.iter_max_closest = c[CTR_ITER_MAX];               st.iter_max_shadow = sh[CTR_ITER_MAX];
+            for (int k = 0; k < CTR_HIST_BINS; ++k) {
+                st.iter_hist_closest[k] = c[CTR_HIST_CLOSEST + k];
+                st.iter_hist_shadow[k] = c[CTR_HIST_SHADOW + k];
+            }
+            const unsigned long long *rec = c + CTR_STRAGGLER_RECORDS;
+            s->stragglers.assign(rec, rec + CTR_STRAGGLER_WORDS * std::min<unsigned long long>(c[CTR_STRAGGLERS], STRAGGLER_MAX));
+            st.instance_visits = c[CTR_INST_VISITS];             st.shadow_instance_visits = c[CTR_INST_VISITS + 1];
+            st.instance_rejects = c[CTR_INST_REJECTS];
+            st.instance_prefiltered = c[CTR_INST_PREFILTERED];
+            st.tie_retraces = c[CTR_TIE_RETRACES];
+            st.guard_rays_closest = c[CTR_GUARD_RAYS];           st.guard_rays_shadow = c[CTR_GUARD_RAYS + 1];
+            st.guard_steps_closest = c[CTR_GUARD_STEPS];         st.guard_steps_shadow = c[CTR_GUARD_STEPS + 1];
+            st.restarts_closest = c[CTR_RESTARTS];               st.restarts_shadow = c[CTR_RESTARTS + 1];
         }
-        s->stragglers.assign(c + 64, c + 64 + 8 * std::min<unsigned long long>(c[48], STRAGGLER_MAX));
-        s->stats.instance_visits = c[49];
-        s->stats.shadow_instance_visits = c[50];
-        s->stats.instance_rejects = c[58];
-        s->stats.instance_prefiltered = c[59];
-        s->stats.tie_retraces = c[51];
-        s->stats.guard_rays_closest = c[52];
-        s->stats.guard_rays_shadow = c[53];
-        s->stats.guard_steps_closest = c[54];
-        s->stats.guard_steps_shadow = c[55];
-        s->stats.restarts_closest = c[56];
-        s->stats.restarts_shadow = c[57];
+        st.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return MTSG_OK;
     }
-    s->stats.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return MTSG_OK;
+};
+
+// the checks and sizing of a render call, then its RenderRun
+int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win = 0, bool multi = false) {
+    int rc;
+    if ((rc = validate(p, s)) != MTSG_OK) return rc;
+    // a handle with a multichannel child set renders through the *_multi
+    // entries only (3m + 2 floats per texel), a plain handle through the others
+    if (s->aovOn && !multi) {
+        g_err = "the scene's integrator is multichannel: use the _multi render entries (channels are not dropped)";
+        return MTSG_ERR_INVALID;
+    }
+    if (multi && !s->aovOn) { g_err = "no multichannel child set is active (mtsg_scene_set_aov)"; return MTSG_ERR_INVALID; }
+    if (multi && p->integrator != MTSG_INTEGRATOR_PATH) { g_err = "multichannel: only `path` and `field` children"; return MTSG_ERR_INVALID; }
+    if ((rc = set_device(s)) != MTSG_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool count = (s->flags & MTSG_FLAG_COUNT) != 0;
+    // bytes of state per path: the field planes join it while fields are active
+    const uint32_t maxPaths = fit_paths(s, PATH_STATE_BYTES + (multi ? (size_t)s->aov.nf * 3 * sizeof(float) : 0));
+    if ((s->dumpL || s->dumpMulti) && (uint64_t)p->tile_w * p->tile_h * p->spp > maxPaths) { g_err = "render_samples: tile does not fit one batch"; return MTSG_ERR_INVALID; }
+    // The debug and counting modes use one lane (multichannel too: one set of field planes)
+    RenderPlan plan = plan_render(p->tile_w, p->tile_h, p->spp, p->tile_stride, p->tile_offset, (uint32_t)s->tileKeys.size(), maxPaths,
+                                  (uint32_t)s->lanes, s->dumpL || s->dumpMulti || count || multi);
+    for (int32_t k : s->tileKeys)
+        if ((uint32_t)k >= plan.allTiles) { g_err = "tile list: a deal key lies outside the rectangle's tiles"; return MTSG_ERR_INVALID; }
+    if ((rc = ensure_batch(s, plan.tilesPerBatch * plan.sppPerBatch * TILE * TILE, (int)plan.lanes)) != MTSG_OK) return rc;
+    if (multi) {
+        if ((rc = ensure_fields(s)) != MTSG_OK) return rc;
+        s->aov.planes = s->fieldPlanes;
+        s->aov.cap = s->fieldCap;
+    }
+    DevIntegrator I{p->max_depth, p->rr_depth, p->strict_normals, p->hide_emitters, p->spp, p->seed, (uint32_t)s->cam.film_w,
+                    make_sampler(s, p->spp)};
+    I.om = p->integrator == MTSG_INTEGRATOR_PATH2_OM ? 1 : 0;
+    I.om_strategy = p->om_strategy;
+    I.om_mis = p->om_mis;
+    I.om_jitter = p->om_jitter;
+    memset(&s->stats, 0, sizeof(s->stats));
+    s->wtLaunches = 0;
+    if ((s->flags & MTSG_FLAG_WAVETIME) && !s->waveTimes)
+        HIP_TRY(hipMalloc((void **)&s->waveTimes, (size_t)WT_WORDS * s->traceGrid * WT_MAX_LAUNCHES * sizeof(unsigned long long)));
+    s->evUsed = 0;
+    s->timed.clear();
+    if (count) HIP_TRY(hipMemsetAsync(s->LP[0].ctr, 0, CTR_WORDS * sizeof(unsigned long long), s->stream));
+    RenderRun R{s, p, I, std::move(plan), film, win, multi, t0};
+    R.count = count;
+    R.fieldsOnly = multi && s->aov.pathChild < 0;
+    R.blockW = p->tile_w + 2 * s->cam.border;
+    R.blockH = p->tile_h + 2 * s->cam.border;
+    // myPath2_OM shades depths 1..maxDepthEye and one more launch books the
+    // emitters its last BSDF rays found
+    R.maxBounces = I.om ? p->max_depth + 1 : (p->max_depth > 0 ? p->max_depth : 1 << 30);
+    // tail mode (k_finish): one lane, not in the instrumented or myPath2_OM modes
+    R.useFinish = s->finishPaths > 0 && R.plan.lanes == 1 && !count && !I.om && !s->knobs;
+    rc = R.open_lanes();
+    if (rc == MTSG_OK) rc = R.run_batches();
+    return R.finish(rc);
+}
+
+// floats of the ImageBlock of a call's rectangle + border: rgb, alpha, weight,
+// or the 3m + 2 channels of the multichannel child set
+size_t block_floats(const mtsg_scene *s, const mtsg_render_params *p, bool multi) {
+    return (size_t)(p->tile_w + 2 * s->cam.border) * (p->tile_h + 2 * s->cam.border) * (multi ? 3 * (size_t)s->aov.m + 2 : 5);
+}
+// mtsg_render / mtsg_render_multi: a device block, cleared, rendered, copied to `out`
+int render_to_host(mtsg_scene *s, const mtsg_render_params *p, float *out, bool multi) {
+    int rc;
+    if ((rc = validate(p, s)) != MTSG_OK) return rc;
+    if ((rc = set_device(s)) != MTSG_OK) return rc;
+    const size_t bytes = block_floats(s, p, multi) * sizeof(float);
+    float *film = nullptr;
+    HIP_TRY(hipMalloc((void **)&film, bytes));
+    hipError_t e = hipMemsetAsync(film, 0, bytes, s->stream);
+    if (e != hipSuccess) { hipFree(film); g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
+    rc = render_impl(s, p, film, 0, multi);
+    if (rc == MTSG_OK) {
+        e = hipMemcpy(out, film, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { g_err = hipGetErrorString(e); rc = MTSG_ERR_DEVICE; }
+    }
+    hipFree(film);
+    return rc;
+}
+// mtsg_render_samples / mtsg_render_samples_multi: the render above into a
+// block that is dropped, with the per-sample dump (RenderRun::dump_*) into `out`
+int render_samples(mtsg_scene *s, const mtsg_render_params *p, float *out, bool multi) {
+    int rc;
+    if ((rc = validate(p, s)) != MTSG_OK) return rc;
+    float *&dump = multi ? s->dumpMulti : s->dumpL;
+    std::vector<float> block(block_floats(s, p, multi));
+    dump = out;
+    rc = render_to_host(s, p, block.data(), multi);
+    dump = nullptr;
+    return rc;
 }
 
 }  // namespace
@@ -1671,34 +1757,13 @@ int mtsg_render_device_tiles_multi(mtsg_scene *s, const mtsg_render_params *p, f
 int mtsg_render_multi(mtsg_scene *s, const mtsg_render_params *p, float *out) {
     if (!s || !out) { g_err = "null argument"; return MTSG_ERR_INVALID; }
     if (!s->aovOn) { g_err = "no multichannel child set is active (mtsg_scene_set_aov)"; return MTSG_ERR_INVALID; }
-    int rc;
-    if ((rc = validate(p, s)) != MTSG_OK) return rc;
-    if ((rc = set_device(s)) != MTSG_OK) return rc;
-    const size_t bytes =
-        (size_t)(p->tile_w + 2 * s->cam.border) * (p->tile_h + 2 * s->cam.border) * (3 * (size_t)s->aov.m + 2) * sizeof(float);
-    float *film = nullptr;
-    HIP_TRY(hipMalloc((void **)&film, bytes));
-    hipError_t e = hipMemsetAsync(film, 0, bytes, s->stream);
-    if (e != hipSuccess) { hipFree(film); g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
-    rc = render_impl(s, p, film, 0, true);
-    if (rc == MTSG_OK) {
-        e = hipMemcpy(out, film, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { g_err = hipGetErrorString(e); rc = MTSG_ERR_DEVICE; }
-    }
-    hipFree(film);
-    return rc;
+    return render_to_host(s, p, out, true);
 }
 
 int mtsg_render_samples_multi(mtsg_scene *s, const mtsg_render_params *p, float *out) {
     if (!s || !out || !p) { g_err = "null argument"; return MTSG_ERR_INVALID; }
     if (!s->aovOn) { g_err = "no multichannel child set is active (mtsg_scene_set_aov)"; return MTSG_ERR_INVALID; }
-    int rcv;
-    if ((rcv = validate(p, s)) != MTSG_OK) return rcv;
-    s->dumpMulti = out;
-    std::vector<float> block((size_t)(p->tile_w + 2 * s->cam.border) * (p->tile_h + 2 * s->cam.border) * (3 * (size_t)s->aov.m + 2));
-    const int rc = mtsg_render_multi(s, p, block.data());
-    s->dumpMulti = nullptr;
-    return rc;
+    return render_samples(s, p, out, true);
 }
 
 int mtsg_render_device(mtsg_scene *s, const mtsg_render_params *p, float *film) {
@@ -1706,19 +1771,11 @@ int mtsg_render_device(mtsg_scene *s, const mtsg_render_params *p, float *film) 
     return render_impl(s, p, film);
 }
 
-static uint32_t tile_count(const mtsg_scene *s, const mtsg_render_params *p) {
-    if (!s->tileKeys.empty()) return (uint32_t)s->tileKeys.size();
-    const uint32_t allTiles = (uint32_t)((p->tile_w + TILE - 1) / TILE) * (uint32_t)((p->tile_h + TILE - 1) / TILE);
-    const uint32_t tstride = p->tile_stride > 1 ? (uint32_t)p->tile_stride : 1u;
-    const uint32_t toffset = p->tile_stride > 1 ? (uint32_t)p->tile_offset : 0u;
-    return toffset < allTiles ? (allTiles - toffset + tstride - 1) / tstride : 0u;
-}
-
 int mtsg_tile_windows(mtsg_scene *s, const mtsg_render_params *p, uint32_t *ntiles, int32_t *window) {
     if (!s || !ntiles || !window) { g_err = "null argument"; return MTSG_ERR_INVALID; }
     int rc;
     if ((rc = validate(p, s)) != MTSG_OK) return rc;
-    *ntiles = tile_count(s, p);
+    *ntiles = plan_render(p->tile_w, p->tile_h, p->spp, p->tile_stride, p->tile_offset, (uint32_t)s->tileKeys.size(), DEFAULT_BATCH_PATHS, 1, true).ntiles;
     *window = TILE + 2 * s->cam.border;
     return MTSG_OK;
 }
@@ -1753,29 +1810,12 @@ int mtsg_render_device_tiles(mtsg_scene *s, const mtsg_render_params *p, float *
 
 int mtsg_render(mtsg_scene *s, const mtsg_render_params *p, float *rgbaw_out) {
     if (!s || !rgbaw_out) { g_err = "null argument"; return MTSG_ERR_INVALID; }
-    int rc;
-    if ((rc = validate(p, s)) != MTSG_OK) return rc;
-    if ((rc = set_device(s)) != MTSG_OK) return rc;
-    const size_t bytes = (size_t)(p->tile_w + 2 * s->cam.border) * (p->tile_h + 2 * s->cam.border) * 5 * sizeof(float);
-    float *film = nullptr;
-    HIP_TRY(hipMalloc((void **)&film, bytes));
-    hipError_t e = hipMemsetAsync(film, 0, bytes, s->stream);
-    if (e != hipSuccess) { hipFree(film); g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
-    rc = render_impl(s, p, film);
-    if (rc == MTSG_OK) {
-        e = hipMemcpy(rgbaw_out, film, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { g_err = hipGetErrorString(e); rc = MTSG_ERR_DEVICE; }
-    }
-    hipFree(film);
-    return rc;
+    return render_to_host(s, p, rgbaw_out, false);
 }
 
 int mtsg_render_samples(mtsg_scene *s, const mtsg_render_params *p, float *L_out) {
     if (!s || !L_out) { g_err = "null argument"; return MTSG_ERR_INVALID; }
-    s->dumpL = L_out;
-    int rc = mtsg_render(s, p, std::vector<float>((size_t)(p->tile_w + 2 * s->cam.border) * (p->tile_h + 2 * s->cam.border) * 5).data());
-    s->dumpL = nullptr;
-    return rc;
+    return render_samples(s, p, L_out, false);
 }
 
 // Ray queries run the production traversal kernel (the one the integrator
@@ -1808,35 +1848,32 @@ static int trace_rays(mtsg_scene *s, uint32_t n, const float *rays, float *t, fl
     } else {
         for (auto &o : out) o = make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    hipError_t e = hipSuccess;
+    DevBuf<float4> da(e, n, a.data()), db(e, n, b.data()), dout(e, n, out.data()), dc(e, c.size(), c.data());
+    DevBuf<uint32_t> hitInst(e, s->ds.inst ? n : 0), tie(e, shadow ? 0 : n), cnt(e, CNT_WORDS);
+    DevBuf<unsigned long long> ctr(e, CTR_WORDS);
+    hitInst.zero();
+    tie.zero();
+    cnt.zero();
+    ctr.zero();
     DevPaths D{};
-    std::vector<void *> mem;
-    auto cleanup = [&]() { for (void *m : mem) hipFree(m); };
-    const size_t f4 = (size_t)n * sizeof(float4);
-    auto alloc = [&](void **ptr, size_t bytes, const void *src) -> hipError_t {
-        hipError_t e = hipMalloc(ptr, bytes);
-        if (e != hipSuccess) return e;
-        mem.push_back(*ptr);
-        return src ? hipMemcpy(*ptr, src, bytes, hipMemcpyHostToDevice) : hipMemset(*ptr, 0, bytes);
-    };
-    float4 **pa = shadow ? &D.sh_o : &D.ray_o, **pb = shadow ? &D.sh_d : &D.ray_d, **po = shadow ? &D.L : &D.hit;
-    hipError_t e = alloc((void **)pa, f4, a.data());
-    if (e == hipSuccess) e = alloc((void **)pb, f4, b.data());
-    if (e == hipSuccess) e = alloc((void **)po, f4, out.data());
-    if (e == hipSuccess && shadow) e = alloc((void **)&D.sh_c, f4, c.data());
-    if (e == hipSuccess && s->ds.inst) e = alloc((void **)&D.hitInst, (size_t)n * sizeof(uint32_t), nullptr);
-    if (e == hipSuccess && !shadow) e = alloc((void **)&D.tie, (size_t)n * sizeof(uint32_t), nullptr);
-    if (e == hipSuccess) e = alloc((void **)&D.cnt, CNT_WORDS * sizeof(uint32_t), nullptr);
-    if (e == hipSuccess) e = alloc((void **)&D.ctr, CTR_WORDS * sizeof(unsigned long long), nullptr);
+    (shadow ? D.sh_o : D.ray_o) = da.p;
+    (shadow ? D.sh_d : D.ray_d) = db.p;
+    (shadow ? D.L : D.hit) = dout.p;
+    D.sh_c = dc.p;
+    D.hitInst = hitInst.p;
+    D.tie = tie.p;
+    D.cnt = cnt.p;
+    D.ctr = ctr.p;
     if (e == hipSuccess && shadow) e = hipMemcpy(D.cnt + CNT_S0, &n, sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { g_err = hipGetErrorString(e); cleanup(); return MTSG_ERR_DEVICE; }
+    if (e != hipSuccess) { g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
     if (shadow) launch_trace(s, false, D, -2, 0, 0u, s->stream);
     else launch_trace(s, false, D, -1, -1, n, s->stream);
     e = hipStreamSynchronize(s->stream);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(out.data(), *po, f4, hipMemcpyDeviceToHost);
+    dout.download(out.data());
     uint32_t err = 0;
     if (e == hipSuccess) e = hipMemcpy(&err, D.cnt + CNT_ERR, sizeof(uint32_t), hipMemcpyDeviceToHost);
-    cleanup();
     if (e != hipSuccess) { g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
     if (err & CNT_ERR_TRAVERSAL) { g_err = traversal_error; return MTSG_ERR_TRAVERSAL; }
     for (uint32_t i = 0; i < n; ++i) {
@@ -1858,22 +1895,14 @@ int mtsg_env_eval(mtsg_scene *s, uint32_t n, const float *dirs, const float *rx,
     if (n == 0) return MTSG_OK;
     int rc;
     if ((rc = set_device(s)) != MTSG_OK) return rc;
-    const size_t bytes = (size_t)n * 3 * sizeof(float);
-    float *dd = nullptr, *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    auto cleanup = [&]() { hipFree(dd); hipFree(dx); hipFree(dy); hipFree(dout); };
-    hipError_t e = hipMalloc((void **)&dd, bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, bytes);
-    if (e == hipSuccess && rx) e = hipMalloc((void **)&dx, bytes);
-    if (e == hipSuccess && ry) e = hipMalloc((void **)&dy, bytes);
-    if (e == hipSuccess) e = hipMemcpy(dd, dirs, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && rx) e = hipMemcpy(dx, rx, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && ry) e = hipMemcpy(dy, ry, bytes, hipMemcpyHostToDevice);
+    const size_t n3 = (size_t)n * 3;
+    hipError_t e = hipSuccess;
+    DevBuf<float> dd(e, n3, dirs), dout(e, n3), dx(e, rx ? n3 : 0, rx), dy(e, ry ? n3 : 0, ry);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_env_eval, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, dd, dx, dy, n, dout);
+        hipLaunchKernelGGL(k_env_eval, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, dd.p, dx.p, dy.p, n, dout.p);
         e = hipStreamSynchronize(s->stream);
     }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
-    cleanup();
+    dout.download(out);
     if (e != hipSuccess) { g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
     return MTSG_OK;
 }
@@ -1884,19 +1913,13 @@ int mtsg_tex_eval(mtsg_scene *s, int tex, uint32_t n, const float *uv, const flo
     if (n == 0) return MTSG_OK;
     int rc;
     if ((rc = set_device(s)) != MTSG_OK) return rc;
-    float *duv_d = nullptr, *dd = nullptr, *dout = nullptr;
-    auto cleanup = [&]() { hipFree(duv_d); hipFree(dd); hipFree(dout); };
-    hipError_t e = hipMalloc((void **)&dd, (size_t)n * 2 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, (size_t)n * 3 * sizeof(float));
-    if (e == hipSuccess && duv) e = hipMalloc((void **)&duv_d, (size_t)n * 4 * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(dd, uv, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && duv) e = hipMemcpy(duv_d, duv, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice);
+    hipError_t e = hipSuccess;
+    DevBuf<float> dd(e, (size_t)n * 2, uv), dout(e, (size_t)n * 3), duv_d(e, duv ? (size_t)n * 4 : 0, duv);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_tex_eval, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, tex, dd, duv_d, n, dout);
+        hipLaunchKernelGGL(k_tex_eval, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, tex, dd.p, duv_d.p, n, dout.p);
         e = hipStreamSynchronize(s->stream);
     }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost);
-    cleanup();
+    dout.download(out);
     if (e != hipSuccess) { g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
     return MTSG_OK;
 }
@@ -1907,25 +1930,16 @@ int mtsg_om_query(mtsg_scene *s, uint32_t n, const float *dirs, const float *o1,
     if (n == 0) return MTSG_OK;
     int rc;
     if ((rc = set_device(s)) != MTSG_OK) return rc;
-    const size_t fb = (size_t)n * 3 * sizeof(float), ib = (size_t)n * sizeof(int32_t);
-    float *dd = nullptr, *d1 = nullptr, *d2 = nullptr;
-    int32_t *di = nullptr, *dv = nullptr;
-    auto cleanup = [&]() { hipFree(dd); hipFree(d1); hipFree(d2); hipFree(di); hipFree(dv); };
-    hipError_t e = hipMalloc((void **)&dd, fb);
-    if (e == hipSuccess) e = hipMalloc((void **)&d1, fb);
-    if (e == hipSuccess) e = hipMalloc((void **)&d2, fb);
-    if (e == hipSuccess) e = hipMalloc((void **)&di, ib);
-    if (e == hipSuccess) e = hipMalloc((void **)&dv, ib);
-    if (e == hipSuccess) e = hipMemcpy(dd, dirs, fb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d1, o1, fb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d2, o2, fb, hipMemcpyHostToDevice);
+    const size_t n3 = (size_t)n * 3;
+    hipError_t e = hipSuccess;
+    DevBuf<float> dd(e, n3, dirs), d1(e, n3, o1), d2(e, n3, o2);
+    DevBuf<int32_t> di(e, n), dv(e, n);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_om_query, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, dd, d1, d2, n, di, dv);
+        hipLaunchKernelGGL(k_om_query, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, dd.p, d1.p, d2.p, n, di.p, dv.p);
         e = hipStreamSynchronize(s->stream);
     }
-    if (e == hipSuccess) e = hipMemcpy(ids, di, ib, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(vis, dv, ib, hipMemcpyDeviceToHost);
-    cleanup();
+    di.download(ids);
+    dv.download(vis);
     if (e != hipSuccess) { g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
     return MTSG_OK;
 }
@@ -1978,22 +1992,17 @@ int mtsg_sampler_draws(mtsg_scene *s, const mtsg_render_params *p, int x, int y,
     for (uint32_t i = 0; i < n; ++i) nOut += kinds[i] == 2 ? 2 : 1;
     DevIntegrator I{p->max_depth, p->rr_depth, p->strict_normals, p->hide_emitters, p->spp, p->seed,
                     (uint32_t)s->cam.film_w, make_sampler(s, p->spp)};
-    int32_t *dk = nullptr;
-    float *dout = nullptr;
-    int *derr = nullptr;
-    auto cleanup = [&]() { hipFree(dk); hipFree(dout); hipFree(derr); };
-    hipError_t e = hipMalloc((void **)&dk, n * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, nOut * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&derr, sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dk, kinds, n * sizeof(int32_t), hipMemcpyHostToDevice);
+    hipError_t e = hipSuccess;
+    DevBuf<int32_t> dk(e, n, kinds);
+    DevBuf<float> dout(e, nOut);
+    DevBuf<int> derr(e, 1);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sampler_draws, dim3(1), dim3(64), 0, s->stream, I, x, y, si, n, dk, dout, derr);
+        hipLaunchKernelGGL(k_sampler_draws, dim3(1), dim3(64), 0, s->stream, I, x, y, si, n, dk.p, dout.p, derr.p);
         e = hipStreamSynchronize(s->stream);
     }
     int err = 0;
-    if (e == hipSuccess) e = hipMemcpy(out, dout, nOut * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&err, derr, sizeof(int), hipMemcpyDeviceToHost);
-    cleanup();
+    dout.download(out);
+    derr.download(&err);
     if (e != hipSuccess) { g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
     if (err) {
         g_err = dim_error(s->samplerType);
