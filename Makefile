@@ -37,7 +37,7 @@ $(HOST_LIB): $(HOST_SRC) $(HOST_HDR) $(SOBOL_BIN)
 # (build/config-linux-gcc.py:7); long specular paths otherwise diverge from
 # the oracle through ulp-level differences (measured: C5 parity 2.0e-3 ->
 # 1.8e-4 relative L1), at no measured cost (C3 1262 vs 1256 Msamples/s).
-# The device library is six translation units built in parallel: mtsg.hip
+# The device library is built from translation units compiled in parallel: mtsg.hip
 # (host side, traversal, camera, splat) and smp_kernels.hip once per sampler
 # (k_shade / k_finish of MTSG_SAMPLER_* = 0..4; unit 0 also answers the
 # k_finish occupancy query).  DEV_EXTRA / DEV_OBJ: measurement variants.
@@ -50,7 +50,7 @@ DEV_FLAGS := -O3 -std=c++17 -fPIC -Wall -ffp-contract=off -fno-slp-vectorize -mu
 # -0.6%; the two-level kernel in mtsg.hip loses 3% under it: DESIGN §3)
 DEV_FLAT_FLAGS ?= -mllvm -amdgpu-sched-strategy=max-memory-clause
 DEV_OBJ   ?= build/dev
-DEV_OBJS  := $(DEV_OBJ)/mtsg.o $(DEV_OBJ)/trace_flat.o $(DEV_OBJ)/fields.o $(DEV_OBJ)/kdbuild.o $(foreach k,0 1 2 3 4,$(DEV_OBJ)/smp_$(k).o)
+DEV_OBJS  := $(DEV_OBJ)/mtsg.o $(DEV_OBJ)/trace_flat.o $(DEV_OBJ)/fields.o $(DEV_OBJ)/direct.o $(DEV_OBJ)/kdbuild.o $(foreach k,0 1 2 3 4,$(DEV_OBJ)/smp_$(k).o)
 $(DEV_OBJ)/mtsg.o: $(PKG)/csrc/mtsg.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
@@ -59,6 +59,10 @@ $(DEV_OBJ)/trace_flat.o: $(PKG)/csrc/trace_flat.hip $(DEV_HDR)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_FLAT_FLAGS) $(DEV_EXTRA) -c -o $@ $<
 # the multichannel integrator's field kernel and block splats (fields.hip)
 $(DEV_OBJ)/fields.o: $(PKG)/csrc/fields.hip $(DEV_HDR)
+	@mkdir -p $(DEV_OBJ)
+	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
+# the direct / ao integrators' shade and resolve kernels (direct.hip)
+$(DEV_OBJ)/direct.o: $(PKG)/csrc/direct.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
 $(DEV_OBJ)/kdbuild.o: $(PKG)/csrc/kdbuild.hip include/mtsg.h

@@ -422,14 +422,19 @@ typedef struct mtsg_render_params {
      * occupancy-map visibility instead of a shadow ray, om_strategy /
      * om_mis its `strategy` (bsdf / nee / mis) and `MISmode` (uniform /
      * balance / power), om_jitter its `jitterSample`; the film is its
-     * per-pixel running mean (a 1-pixel box) */
+     * per-pixel running mean (a 1-pixel box);
+     * MTSG_INTEGRATOR_DIRECT = MIDirectIntegrator (direct.cpp) and
+     * MTSG_INTEGRATOR_AO = AmbientOcclusionIntegrator (ao.cpp): their sample
+     * counts travel in the descriptor that mtsg_scene_set_direct gives the handle;
+     * strict_normals and hide_emitters apply to `direct`, max_depth and
+     * rr_depth to neither (they must still be valid values) */
     int32_t integrator;
     int32_t om_strategy;
     int32_t om_mis;
     int32_t om_jitter;
 } mtsg_render_params;
 
-enum { MTSG_INTEGRATOR_PATH = 0, MTSG_INTEGRATOR_PATH2_OM = 1 };
+enum { MTSG_INTEGRATOR_PATH = 0, MTSG_INTEGRATOR_PATH2_OM = 1, MTSG_INTEGRATOR_DIRECT = 2, MTSG_INTEGRATOR_AO = 3 };
 enum { MTSG_OM_STRATEGY_BSDF = 0, MTSG_OM_STRATEGY_NEE = 1, MTSG_OM_STRATEGY_MIS = 2 };
 enum { MTSG_OM_MIS_UNIFORM = 0, MTSG_OM_MIS_BALANCE = 1, MTSG_OM_MIS_POWER = 2 };
 
@@ -744,7 +749,12 @@ void mtsg_kd_free(mtsg_kd_tree *tree);
  * = 1 (next1D, one float out) or 2 (next2D, two floats), in call order, as
  * Sampler::next1D / next2D after Sampler::generate(pos) + setSampleIndex(s)
  * (src/librender/sampler.cpp; samplers per mtsg_sampler).  params gives spp
- * and seed.  The first next2D is the camera's pixel jitter. */
+ * and seed.  The first next2D is the camera's pixel jitter.
+ * kinds[i] = -n (n >= 2) is next2DArray(n), 2n floats out: the i-th such
+ * entry reads the i-th array the handle's mtsg_direct_desc requests (emitter
+ * array, then BSDF array; `ao`: its one array) and n must be that request's
+ * size.  With a descriptor set, the regular draws of halton and sobol skip the
+ * dimensions reserved to the arrays, as in a render. */
 int  mtsg_sampler_draws(mtsg_scene *scene, const mtsg_render_params *params, int x, int y, uint32_t s,
                         uint32_t n, const int32_t *kinds, float *out);
 
@@ -845,6 +855,28 @@ int  mtsg_render_device_tiles_multi(mtsg_scene *scene, const mtsg_render_params 
 /* mtsg_render_samples with 3m + 1 floats per sample: the children's
  * spectra, then alpha. */
 int  mtsg_render_samples_multi(mtsg_scene *scene, const mtsg_render_params *params, float *out);
+
+/* ---- direct / ao integrators ------------------------------------------------
+ * Mitsuba's `direct` (src/integrators/direct/direct.cpp:91-330) and `ao`
+ * (src/integrators/direct/ao.cpp:44-140) integrators: per camera sample a fan
+ * of emitter_samples shadow rays and bsdf_samples BSDF rays (direct), or of
+ * ao_samples cosine-weighted occlusion rays of length ao_ray_length (ao; the
+ * value of a miss is 1).  A technique with more than one sample takes its
+ * random numbers from a 2D sample array of the sampler (request2DArray /
+ * next2DArray); hammersley has none.  The film entries, tile splits, the tile
+ * callback and mtsg_cancel work as for `path`; the block is the same
+ * [R, G, B, alpha, weight].  The numbers `path` lacks travel beside the scene
+ * descriptor, whose layout they leave alone; mtsh_scene_direct fills them. */
+typedef struct mtsg_direct_desc {
+    uint32_t emitter_samples, bsdf_samples;  /* direct */
+    uint32_t ao_samples;                     /* ao */
+    float    ao_ray_length;                  /* ao: > 0 */
+} mtsg_direct_desc;
+
+/* Set (or, desc == NULL, remove) the descriptor of a scene handle.  A render
+ * with MTSG_INTEGRATOR_DIRECT or MTSG_INTEGRATOR_AO and no descriptor returns
+ * MTSG_ERR_INVALID; `path` renders ignore it. */
+int  mtsg_scene_set_direct(mtsg_scene *scene, const mtsg_direct_desc *desc);
 
 void mtsg_scene_destroy(mtsg_scene *scene);
 

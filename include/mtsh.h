@@ -42,7 +42,9 @@ enum {
                                       /* FILM_CROP is given too)                    */
     MTSH_OVERRIDE_SAMPLE_COUNT = 2,   /* Sampler::getSampleCount                    */
     MTSH_OVERRIDE_INTEGRATOR   = 4,   /* MonteCarloIntegrator m_maxDepth, m_rrDepth, */
-                                      /* m_strictNormals, m_hideEmitters            */
+                                      /* m_strictNormals, m_hideEmitters; a `direct` */
+                                      /* scene takes the last two, the depths are   */
+                                      /* neither checked nor used                   */
     MTSH_OVERRIDE_FILM_CROP    = 8    /* Film::getCropOffset / getCropSize          */
                                       /* (film.cpp:36-48)                           */
 };
@@ -219,6 +221,13 @@ const mtsg_scene_desc *mtsh_scene_desc(const mtsh_scene *scene);
  * mtsg_scene_set_aov; owned by the scene), or NULL when its integrator is
  * not `multichannel`. */
 const mtsg_aov_desc *mtsh_scene_aov(const mtsh_scene *scene);
+
+/* The direct / ao descriptor of the scene (mtsg.h, for mtsg_scene_set_direct):
+ * returns 1 and fills *out (may be NULL) when the scene's integrator is
+ * `direct` or `ao`, else 0.  ao_ray_length is resolved: a negative or missing
+ * `rayLength` is half the radius of the scene's bounding sphere (ao.cpp:72-82;
+ * the kd-tree AABB expanded by the sensor position, scene.cpp:412-440). */
+int mtsh_scene_direct(const mtsh_scene *scene, mtsg_direct_desc *out);
 
 /* The film's pixelFormat entries and channel names (hdrfilm.cpp:216-295).
  * formats (may be NULL) receives up to capacity MTSH_FORMAT_* ids, the count

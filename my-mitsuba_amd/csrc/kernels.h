@@ -259,6 +259,35 @@ struct FieldsLaunch {
 void launch_fields(const FieldsLaunch &a);        // k_fields: after the bounce-0 trace launch
 void launch_splat_multi(const FieldsLaunch &a);   // the `path` child (or alpha and weight alone), then the fields
 
+// direct / ao integrators (direct.hip, its own translation unit): the fan of
+// shadow and BSDF rays of a batch's camera samples.  F holds the rays, their
+// hits and the shadow rays' private accumulation cells (F.Lp) and shares the
+// batch's counters (cnt, ctr) with its DevPaths; the other arrays are per ray.
+struct DevDirect {
+    int ao;                          // 0: direct, 1: ao
+    uint32_t ne, nb;                 // shadow / BSDF rays per camera sample (ao: ne = shadingSamples, nb = 0)
+    float rayLength;                 // ao
+    float fracLum, fracBSDF, weightLum, weightBSDF;   // direct.cpp:128-136
+    DevArrays arrays;                // the sampler's 2D array requests, in configureSampler's order
+    DevPaths F;                      // ray_o / ray_d / hit / hitInst / tie: BSDF ray slot * nb + j;
+                                     // sh_o / sh_d / sh_c: shadow rays, compacted; Lp: cell slot * ne + i
+    float4 *val;                     // BSDF ray: bsdfVal, bsdfPdf
+    uint32_t *flag;                  // BSDF ray: 1 = sampled a delta component
+};
+struct DirectLaunch {
+    hipStream_t stream;
+    const DevScene *S;
+    const DevIntegrator *I;
+    const DevBatch *B;
+    const DevPaths *P;
+    const DevDirect *D;
+    int hasAlpha;
+    bool env, ext;   // as ShadeLaunch
+    int mats;        // the scene's material classes (MAT_*), or MATS_ALL
+};
+void launch_direct_shade(const DirectLaunch &a);     // after the camera rays' trace launch: the fan
+void launch_direct_resolve(const DirectLaunch &a);   // after the fan's trace launch: P.L
+
 }  // namespace mtsg
 
 using namespace mtsg;

@@ -160,6 +160,14 @@ struct mtsg_scene {
     uint32_t nShapes = 0;
     std::vector<int32_t> bsdfTexture; // mtsg_bsdf::texture of every record (host copy)
     float *dumpMulti = nullptr;       // mtsg_render_samples_multi
+    // direct / ao integrators (mtsg_scene_set_direct; direct.hip): the
+    // descriptor and the fan buffers of a batch, allocated by the first such
+    // render (one lane) and freed with the path state
+    bool directOn = false;
+    mtsg_direct_desc direct{};
+    DevDirect fan{};
+    std::vector<void *> fanAllocs;
+    size_t fanClosest = 0, fanShadow = 0;   // BSDF / shadow rays the buffers hold
 };
 
 namespace {
@@ -169,7 +177,21 @@ int set_device(mtsg_scene *s) {
     return MTSG_OK;
 }
 
+// bytes of a sample's fan: per BSDF ray origin, direction, hit, tie entry,
+// instance, bsdfVal + pdf, flag; per shadow ray origin, direction,
+// contribution and its cell
+constexpr size_t FAN_CLOSEST_BYTES = 32 + 16 + 4 + 4 + 16 + 4, FAN_SHADOW_BYTES = 48 + 16;
+size_t fan_bytes(uint32_t ne, uint32_t nb) { return nb * FAN_CLOSEST_BYTES + ne * FAN_SHADOW_BYTES; }
+
+void free_fan(mtsg_scene *s) {
+    for (void *p : s->fanAllocs) hipFree(p);
+    s->fanAllocs.clear();
+    s->fan = DevDirect{};
+    s->fanClosest = s->fanShadow = 0;
+}
+
 void free_batch(mtsg_scene *s) {
+    free_fan(s);
     for (void *p : s->batchAllocs) hipFree(p);
     s->batchAllocs.clear();
     if (s->fieldPlanes) hipFree(s->fieldPlanes);
@@ -209,6 +231,32 @@ int ensure_batch(mtsg_scene *s, uint32_t paths, int lanes) {
     }
     s->capacity = paths;
     s->lanesAlloc = lanes;
+    return MTSG_OK;
+}
+
+// the fan buffers of a direct / ao batch of `slots` samples (lane 0's)
+int ensure_fan(mtsg_scene *s, size_t slots, uint32_t ne, uint32_t nb) {
+    const size_t nC = slots * nb, nS = slots * ne;
+    if (s->fanClosest >= nC && s->fanShadow >= nS) return MTSG_OK;
+    free_fan(s);
+    auto alloc = [&](size_t bytes, void **p) -> int {
+        *p = nullptr;
+        if (!bytes) return MTSG_OK;
+        HIP_TRY(hipMalloc(p, bytes));
+        s->fanAllocs.push_back(*p);
+        return MTSG_OK;
+    };
+    DevDirect &D = s->fan;
+    DevPaths &F = D.F;
+    int rc;
+#define A(ptr, n, T) if ((rc = alloc((n) * sizeof(T), (void **)&ptr)) != MTSG_OK) return rc
+    A(F.ray_o, nC, float4); A(F.ray_d, nC, float4); A(F.hit, nC, float4); A(F.tie, nC, uint32_t);
+    if (s->ds.inst) { A(F.hitInst, nC, uint32_t); }
+    A(D.val, nC, float4); A(D.flag, nC, uint32_t);
+    A(F.sh_o, nS, float4); A(F.sh_d, nS, float4); A(F.sh_c, nS, float4); A(F.Lp, nS, float4);
+#undef A
+    s->fanClosest = nC;
+    s->fanShadow = nS;
     return MTSG_OK;
 }
 
@@ -433,6 +481,26 @@ const char *dim_error(int sampler) {
                : "Lookup dimension exceeds the prime number table size! You may have to reduce the 'maxDepth' parameter of your integrator.";
 }
 
+// Mitsuba's Log(EError) of HammersleySampler::request2DArray (hammersley.cpp:297-301)
+constexpr uint64_t MAX_ARRAY_ENTRIES = 1ull << 31;   // spp x array size (sampler.h smp_array2D)
+const char *const hammersley_array_error =
+    "request2DArray(): Not supported for the Hammersley QMC sequence! If you used this sampler together with the 'direct' or 'ao' "
+    "integrators, you will have to set the 'shadingSamples' parameter to 1 to use this sampler.";
+
+// the fan of a direct / ao render: shadow and BSDF rays per camera sample
+void fan_counts(const mtsg_scene *s, const mtsg_render_params *p, uint32_t &ne, uint32_t &nb) {
+    ne = nb = 0;
+    if (p->integrator == MTSG_INTEGRATOR_DIRECT) { ne = s->direct.emitter_samples; nb = s->direct.bsdf_samples; }
+    else if (p->integrator == MTSG_INTEGRATOR_AO) ne = s->direct.ao_samples;
+}
+// the 2D array requests of its configureSampler (direct.cpp:138-144, ao.cpp:65-70)
+DevArrays fan_arrays(uint32_t ne, uint32_t nb) {
+    DevArrays A{};
+    if (ne > 1) A.n[A.count++] = ne;
+    if (nb > 1) A.n[A.count++] = nb;
+    return A;
+}
+
 int validate(const mtsg_render_params *p, const mtsg_scene *s) {
     if (!p) { g_err = "null params"; return MTSG_ERR_INVALID; }
     if (p->spp == 0) { g_err = "spp must be > 0"; return MTSG_ERR_INVALID; }
@@ -451,7 +519,26 @@ int validate(const mtsg_render_params *p, const mtsg_scene *s) {
         g_err = "invalid tile_stride / tile_offset";
         return MTSG_ERR_INVALID;
     }
-    if (p->integrator != MTSG_INTEGRATOR_PATH && p->integrator != MTSG_INTEGRATOR_PATH2_OM) { g_err = "unknown integrator"; return MTSG_ERR_INVALID; }
+    if (p->integrator < MTSG_INTEGRATOR_PATH || p->integrator > MTSG_INTEGRATOR_AO) { g_err = "unknown integrator"; return MTSG_ERR_INVALID; }
+    if (p->integrator == MTSG_INTEGRATOR_DIRECT || p->integrator == MTSG_INTEGRATOR_AO) {
+        const bool ao = p->integrator == MTSG_INTEGRATOR_AO;
+        if (!s->directOn) {
+            g_err = std::string(ao ? "ao" : "direct") + ": the handle has no mtsg_direct_desc (mtsg_scene_set_direct)";
+            return MTSG_ERR_INVALID;
+        }
+        const mtsg_direct_desc &d = s->direct;
+        if (!ao && d.emitter_samples + d.bsdf_samples == 0) { g_err = "direct: emitterSamples + bsdfSamples must be greater than zero"; return MTSG_ERR_INVALID; }
+        if (ao && (d.ao_samples == 0 || !(d.ao_ray_length > 0))) { g_err = "ao: shadingSamples and rayLength must be greater than zero"; return MTSG_ERR_INVALID; }
+        const bool arrays = ao ? d.ao_samples > 1 : (d.emitter_samples > 1 || d.bsdf_samples > 1);
+        if (arrays && s->samplerType == MTSG_SAMPLER_HAMMERSLEY) {
+            g_err = hammersley_array_error;
+            return MTSG_ERR_INVALID;
+        }
+        // one array's entry s n + k indexes 32-bit sequences, and the ldsampler's
+        // shuffle walks a power of two that holds spp n
+        const uint64_t most = ao ? d.ao_samples : std::max(d.emitter_samples, d.bsdf_samples);
+        if (most * p->spp > MAX_ARRAY_ENTRIES) { g_err = "sample arrays: spp x array size exceeds 2^31"; return MTSG_ERR_INVALID; }
+    }
     if (p->integrator == MTSG_INTEGRATOR_PATH2_OM) {
         if (!s->ds.om) { g_err = "myPath2_OM: the scene has no occupancy maps"; return MTSG_ERR_INVALID; }
         if (s->samplerType != MTSG_SAMPLER_INDEPENDENT) { g_err = "myPath2_OM: only the independent sampler is supported"; return MTSG_ERR_INVALID; }
@@ -472,7 +559,8 @@ uint32_t fit_paths(const mtsg_scene *s, size_t stateBytes) {
     uint32_t maxPaths = DEFAULT_BATCH_PATHS;
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-        const size_t held = (size_t)s->capacity * s->lanesAlloc * PATH_STATE_BYTES + (size_t)s->fieldCap * s->fieldCount * 3 * sizeof(float);
+        const size_t held = (size_t)s->capacity * s->lanesAlloc * PATH_STATE_BYTES + (size_t)s->fieldCap * s->fieldCount * 3 * sizeof(float) +
+                            s->fanClosest * FAN_CLOSEST_BYTES + s->fanShadow * FAN_SHADOW_BYTES;
         // 3/4 of the free HBM (288 GB on an MI355X: 768M paths, C5's three
         // batches of 713M); the rest stays for the scene and other users
         const size_t fit = (size_t)((freeB + held) * 0.75 / stateBytes);
@@ -501,6 +589,7 @@ struct RenderRun {
     bool count = false;
     bool fieldsOnly = false;   // multichannel without a `path` child
     bool useFinish = false;    // tail mode (k_finish)
+    bool direct = false;       // direct / ao: camera rays, the fan, resolve (direct.hip)
     int blockW = 0, blockH = 0, maxBounces = 0;
     struct Lane {
         DevBatch B;
@@ -528,6 +617,10 @@ struct RenderRun {
         return DevBatch{p->tile_x, p->tile_y, p->tile_w, p->tile_h, (int)plan.tilesX, (int)b.tile0, (int)b.ntiles,
                         (int)plan.tstride, (int)plan.toffset, PLAN_DEAL_SKEW, b.s0, b.ns, b.nslots,
                         s->tileKeys.empty() ? nullptr : s->tileKeysDev};
+    }
+    DirectLaunch direct_args(uint32_t l) const {
+        return DirectLaunch{s->lstream[l], &s->ds, &I, &lane[l].B, &s->LP[l], &s->fan, s->cam.has_alpha, s->ds.has_env != 0, s->extBsdfs,
+                            s->shadeGeneric ? (int)MATS_ALL : s->mats};
     }
     FieldsLaunch fields(uint32_t l) const {
         return FieldsLaunch{s->lstream[l], &s->ds, &s->cam, &I, &lane[l].B, &s->LP[l], &s->aov, film, blockW, blockH, win};
@@ -607,6 +700,19 @@ struct RenderRun {
             // copy carries the traversal's error word
             if (fieldsOnly) return end_lane(l, 0);
         }
+        if (direct) {
+            // the fan of the camera samples (work list: the identity), one
+            // trace launch over its BSDF rays (identity over slot * nb + j) and
+            // its shadow rays (S0), then the sum per sample.  The shadow rays'
+            // cells start at zero; the fan shares the lane's counters.
+            const DevDirect &D = s->fan;
+            if (D.ne) HIP_TRY(hipMemsetAsync(D.F.Lp, 0, (size_t)L.B.nslots * D.ne * sizeof(float4), st));
+            timed_launch(s, K_SHADE, st, [&]() { launch_direct_shade(direct_args(l)); });
+            hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, st, P.cnt, -1, -1);
+            timed_launch(s, K_CLOSEST, st, [&]() { launch_trace(s, count, D.F, D.nb ? -1 : -2, 0, L.B.nslots * D.nb, st); });
+            timed_launch(s, K_SHADE, st, [&]() { launch_direct_resolve(direct_args(l)); });
+            return end_lane(l, 0);
+        }
         if (useFinish && b >= 1) {
             // the count of this bounce's paths is known once bounce b-1 is
             // done (the GPU meanwhile runs this bounce's trace): few left ->
@@ -669,13 +775,20 @@ struct RenderRun {
             Lane &L = lane[l];
             if (L.last < 0) continue;
             HIP_TRY(hipEventSynchronize(L.cntEv[L.last & 1]));
-            if (fieldsOnly) {
+            if (fieldsOnly || direct) {
                 // one closest launch per batch, one camera ray per sample inside the rectangle
                 s->stats.launches_trace_closest++;
                 for (int tl = 0; tl < L.B.ntiles; ++tl) {
                     int x, y, w, h;
                     tile_rect(hostKey(L.B.tile0 + tl), L.B, x, y, w, h);
                     s->stats.rays_closest += (uint64_t)w * h * L.B.ns;
+                }
+                if (direct) {
+                    // the fan's launch: the BSDF rays k_direct_shade sent (its
+                    // count in Q1) and the shadow rays it appended (S0)
+                    s->stats.launches_trace_closest++;
+                    s->stats.rays_closest += hostCnt(l, 0)[CNT_Q1];
+                    s->stats.rays_shadow += hostCnt(l, 0)[CNT_S0];
                 }
             } else {
                 account(l, L.last);
@@ -878,15 +991,38 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
     if ((rc = set_device(s)) != MTSG_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const bool count = (s->flags & MTSG_FLAG_COUNT) != 0;
-    // bytes of state per path: the field planes join it while fields are active
-    const uint32_t maxPaths = fit_paths(s, PATH_STATE_BYTES + (multi ? (size_t)s->aov.nf * 3 * sizeof(float) : 0));
+    // direct / ao: the fan of ne shadow and nb BSDF rays per camera sample
+    const bool direct = p->integrator == MTSG_INTEGRATOR_DIRECT || p->integrator == MTSG_INTEGRATOR_AO;
+    uint32_t ne, nb;
+    fan_counts(s, p, ne, nb);
+    // bytes of state per path: the field planes join it while fields are
+    // active, the fan's rays and cells in a direct / ao render
+    const uint32_t maxPaths = fit_paths(s, PATH_STATE_BYTES + (multi ? (size_t)s->aov.nf * 3 * sizeof(float) : 0) + fan_bytes(ne, nb));
     if ((s->dumpL || s->dumpMulti) && (uint64_t)p->tile_w * p->tile_h * p->spp > maxPaths) { g_err = "render_samples: tile does not fit one batch"; return MTSG_ERR_INVALID; }
-    // The debug and counting modes use one lane (multichannel too: one set of field planes)
+    // The debug and counting modes use one lane (multichannel too: one set of
+    // field planes; direct / ao: one set of fan buffers)
     RenderPlan plan = plan_render(p->tile_w, p->tile_h, p->spp, p->tile_stride, p->tile_offset, (uint32_t)s->tileKeys.size(), maxPaths,
-                                  (uint32_t)s->lanes, s->dumpL || s->dumpMulti || count || multi);
+                                  (uint32_t)s->lanes, s->dumpL || s->dumpMulti || count || multi || direct, direct ? ne + nb : 1u);
     for (int32_t k : s->tileKeys)
         if ((uint32_t)k >= plan.allTiles) { g_err = "tile list: a deal key lies outside the rectangle's tiles"; return MTSG_ERR_INVALID; }
+    if (direct && s->dumpL && plan.batches.size() > 1) { g_err = "render_samples: tile does not fit one batch"; return MTSG_ERR_INVALID; }
     if ((rc = ensure_batch(s, plan.tilesPerBatch * plan.sppPerBatch * TILE * TILE, (int)plan.lanes)) != MTSG_OK) return rc;
+    if (direct) {
+        if ((rc = ensure_fan(s, (size_t)plan.tilesPerBatch * plan.sppPerBatch * TILE * TILE, ne, nb)) != MTSG_OK) return rc;
+        DevDirect &D = s->fan;
+        D.ao = p->integrator == MTSG_INTEGRATOR_AO ? 1 : 0;
+        D.ne = ne;
+        D.nb = nb;
+        D.rayLength = s->direct.ao_ray_length;
+        // MIDirectIntegrator::configure (direct.cpp:128-136)
+        D.weightBSDF = 1 / (float)nb;
+        D.weightLum = 1 / (float)ne;
+        D.fracBSDF = nb / (float)(ne + nb);
+        D.fracLum = ne / (float)(ne + nb);
+        D.arrays = fan_arrays(ne, nb);
+        D.F.cnt = s->LP[0].cnt;
+        D.F.ctr = s->LP[0].ctr;
+    }
     if (multi) {
         if ((rc = ensure_fields(s)) != MTSG_OK) return rc;
         s->aov.planes = s->fieldPlanes;
@@ -914,7 +1050,9 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
     // emitters its last BSDF rays found
     R.maxBounces = I.om ? p->max_depth + 1 : (p->max_depth > 0 ? p->max_depth : 1 << 30);
     // tail mode (k_finish): one lane, not in the instrumented or myPath2_OM modes
-    R.useFinish = s->finishPaths > 0 && R.plan.lanes == 1 && !count && !I.om && !s->knobs;
+    R.useFinish = s->finishPaths > 0 && R.plan.lanes == 1 && !count && !I.om && !s->knobs && !direct;
+    R.direct = direct;
+    if (direct) R.maxBounces = 1;
     rc = R.open_lanes();
     if (rc == MTSG_OK) rc = R.run_batches();
     return R.finish(rc);
@@ -1744,6 +1882,20 @@ int mtsg_scene_set_aov(mtsg_scene *s, const mtsg_aov_desc *d) {
     return MTSG_OK;
 }
 
+int mtsg_scene_set_direct(mtsg_scene *s, const mtsg_direct_desc *d) {
+    if (!s) { g_err = "null scene"; return MTSG_ERR_INVALID; }
+    if (!d) { s->directOn = false; s->direct = mtsg_direct_desc{}; return MTSG_OK; }
+    // one sample's fan must leave room for a tile of samples in a batch (render_plan.h)
+    if ((uint64_t)d->emitter_samples + d->bsdf_samples > PLAN_MAX_FAN || d->ao_samples > PLAN_MAX_FAN) {
+        g_err = "direct / ao: more than " + std::to_string(PLAN_MAX_FAN) + " shading samples per camera sample";
+        return MTSG_ERR_INVALID;
+    }
+    if (d->ao_samples && !(d->ao_ray_length > 0)) { g_err = "ao: rayLength must be greater than zero (mtsh_scene_direct resolves the default)"; return MTSG_ERR_INVALID; }
+    s->direct = *d;
+    s->directOn = true;
+    return MTSG_OK;
+}
+
 int mtsg_render_device_multi(mtsg_scene *s, const mtsg_render_params *p, float *film) {
     if (!s || !film) { g_err = "null argument"; return MTSG_ERR_INVALID; }
     return render_impl(s, p, film, 0, true);
@@ -1951,12 +2103,30 @@ void set_last_error(const std::string &e) { g_err = e; }   // kdbuild.hip
 }
 
 namespace {
-__global__ void k_sampler_draws(DevIntegrator I, int x, int y, uint32_t s, uint32_t n, const int32_t *kinds, float *out,
+// A: the handle's sample array requests; a negative kind reads the next one
+__global__ void k_sampler_draws(DevIntegrator I, DevArrays A, int x, int y, uint32_t s, uint32_t n, const int32_t *kinds, float *out,
                                 int *err) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     PathSampler p = path_sampler(I, x, y, s, 0, 0);
+    uint32_t req = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const int t = I.smp.type;
+        if (kinds[i] < 0) {   // next2DArray(-kinds[i])
+            const uint32_t r = req++, m = (uint32_t)(-kinds[i]);
+            const uint64_t pix = pixel_index(I, p);
+            for (uint32_t k = 0; k < m; ++k) {
+                float a, b;
+                if (t == MTSG_SAMPLER_HALTON) smp_array2D<MTSG_SAMPLER_HALTON>(I.smp, p, I.seed, pix, I.spp, r, m, k, a, b);
+                else if (t == MTSG_SAMPLER_LDSAMPLER) smp_array2D<MTSG_SAMPLER_LDSAMPLER>(I.smp, p, I.seed, pix, I.spp, r, m, k, a, b);
+                else if (t == MTSG_SAMPLER_SOBOL) smp_array2D<MTSG_SAMPLER_SOBOL>(I.smp, p, I.seed, pix, I.spp, r, m, k, a, b);
+                else smp_array2D<MTSG_SAMPLER_INDEPENDENT>(I.smp, p, I.seed, pix, I.spp, r, m, k, a, b);
+                *out++ = a;
+                *out++ = b;
+            }
+            continue;
+        }
+        if (t == MTSG_SAMPLER_HALTON) smp_skip_arrays<MTSG_SAMPLER_HALTON>(p, A.count, kinds[i] == 2 ? 2 : 1);
+        else if (t == MTSG_SAMPLER_SOBOL) smp_skip_arrays<MTSG_SAMPLER_SOBOL>(p, A.count, kinds[i] == 2 ? 2 : 1);
         if (kinds[i] == 2) {
             float a, b;
             if (t == MTSG_SAMPLER_HALTON) next2D<MTSG_SAMPLER_HALTON>(I, p, a, b);
@@ -1988,8 +2158,27 @@ int mtsg_sampler_draws(mtsg_scene *s, const mtsg_render_params *p, int x, int y,
     if (n == 0) return MTSG_OK;
     int rc;
     if ((rc = set_device(s)) != MTSG_OK) return rc;
-    uint32_t nOut = 0;
-    for (uint32_t i = 0; i < n; ++i) nOut += kinds[i] == 2 ? 2 : 1;
+    // the array requests of the handle's descriptor (`direct`'s when it has
+    // any, else `ao`'s); kinds[i] = -n reads them in order
+    DevArrays A{};
+    if (s->directOn) {
+        A = fan_arrays(s->direct.emitter_samples, s->direct.bsdf_samples);
+        if (!A.count) A = fan_arrays(s->direct.ao_samples, 0);
+    }
+    uint32_t nOut = 0, req = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (kinds[i] < 0) {
+            if (s->samplerType == MTSG_SAMPLER_HAMMERSLEY) { g_err = hammersley_array_error; return MTSG_ERR_INVALID; }
+            if (kinds[i] > -2 || req >= A.count || A.n[req] != (uint32_t)(-kinds[i]) || (uint64_t)A.n[req] * p->spp > MAX_ARRAY_ENTRIES) {
+                g_err = "mtsg_sampler_draws: kinds[i] = -n must name the next sample array of the handle's mtsg_direct_desc";
+                return MTSG_ERR_INVALID;
+            }
+            ++req;
+            nOut += 2 * (uint32_t)(-kinds[i]);
+        } else {
+            nOut += kinds[i] == 2 ? 2 : 1;
+        }
+    }
     DevIntegrator I{p->max_depth, p->rr_depth, p->strict_normals, p->hide_emitters, p->spp, p->seed,
                     (uint32_t)s->cam.film_w, make_sampler(s, p->spp)};
     hipError_t e = hipSuccess;
@@ -1997,7 +2186,7 @@ int mtsg_sampler_draws(mtsg_scene *s, const mtsg_render_params *p, int x, int y,
     DevBuf<float> dout(e, nOut);
     DevBuf<int> derr(e, 1);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sampler_draws, dim3(1), dim3(64), 0, s->stream, I, x, y, si, n, dk.p, dout.p, derr.p);
+        hipLaunchKernelGGL(k_sampler_draws, dim3(1), dim3(64), 0, s->stream, I, A, x, y, si, n, dk.p, dout.p, derr.p);
         e = hipStreamSynchronize(s->stream);
     }
     int err = 0;

@@ -20,11 +20,19 @@ constexpr uint32_t PLAN_TILE_SLOTS = PLAN_TILE * PLAN_TILE;       // path slots 
 // measurement override is gone: a rank with another rotation would put
 // its tiles in the wrong places without an error)
 constexpr int PLAN_DEAL_SKEW = 1;
+// direct / ao renders send a fan of `fan` rays per path slot (shadow + BSDF
+// rays; `path`: 1).  A batch's fan is indexed with 31 bits (bit 31 of a shadow
+// ray's target marks a final slot, kernels.h shadow_unoccluded), so a batch
+// holds at most PLAN_MAX_RAYS / fan slots, and one tile of one sample fits
+// whatever the fan is up to PLAN_MAX_FAN.
+constexpr uint32_t PLAN_MAX_RAYS = 1u << 31;
+constexpr uint32_t PLAN_MAX_FAN = PLAN_MAX_RAYS / PLAN_TILE_SLOTS / 128;   // 65536
 
 struct PlanBatch {
     uint32_t tile0, ntiles;   // virtual tile range
     uint32_t s0, ns;          // sample range
     uint32_t nslots;          // ntiles * ns * PLAN_TILE_SLOTS
+    uint32_t nrays;           // nslots * fan: the batch's fan entries (<= PLAN_MAX_RAYS)
 };
 
 struct RenderPlan {
@@ -34,16 +42,19 @@ struct RenderPlan {
     uint32_t lanes;                    // batches in flight
     uint32_t sppPerBatch, tilesPerBatch;
     uint32_t tileGroups;               // planned tile ranges: a multiple of lanes, or one per tile
+    uint32_t fan;                      // rays per path slot
     std::vector<PlanBatch> batches;    // tile-major, then sample-major
 };
 
 // tile_w x tile_h: the rectangle; listedKeys: the number of deal keys of
 // mtsg_set_tile_list (0: none, the call takes tile_stride / tile_offset);
 // maxPaths: the path slots in flight over all lanes, after the memory fit;
-// singleLane: the debug, counting and multichannel modes
+// singleLane: the debug, counting, multichannel and direct / ao modes;
+// fan: 1 .. PLAN_MAX_FAN (maxPaths already counts the fan's bytes per slot)
 inline RenderPlan plan_render(int tile_w, int tile_h, uint32_t spp, int tile_stride, int tile_offset, uint32_t listedKeys,
-                              uint32_t maxPaths, uint32_t lanes, bool singleLane) {
+                              uint32_t maxPaths, uint32_t lanes, bool singleLane, uint32_t fan = 1) {
     RenderPlan R;
+    R.fan = std::max(1u, std::min(fan, PLAN_MAX_FAN));
     const uint32_t tilesY = (uint32_t)(tile_h + PLAN_TILE - 1) / PLAN_TILE;
     R.tilesX = (uint32_t)(tile_w + PLAN_TILE - 1) / PLAN_TILE;
     R.allTiles = R.tilesX * tilesY;
@@ -54,7 +65,7 @@ inline RenderPlan plan_render(int tile_w, int tile_h, uint32_t spp, int tile_str
     // in lock step, so one lane's launch tail (its slowest rays) overlaps the
     // other lane's launch.
     R.lanes = (singleLane || R.ntiles < 2) ? 1u : lanes;
-    const uint32_t lanePaths = std::max<uint32_t>(PLAN_TILE_SLOTS, maxPaths / R.lanes);
+    const uint32_t lanePaths = std::max<uint32_t>(PLAN_TILE_SLOTS, std::min(maxPaths / R.lanes, PLAN_MAX_RAYS / R.fan));
     R.sppPerBatch = std::max(1u, std::min(spp, lanePaths / PLAN_TILE_SLOTS));
     // equal-sized batches, a multiple of the lane count: a nearly empty last
     // batch costs a full set of bounce launches (and their tails) for a
@@ -71,6 +82,7 @@ inline RenderPlan plan_render(int tile_w, int tile_h, uint32_t spp, int tile_str
             B.s0 = s0;
             B.ns = std::min(R.sppPerBatch, spp - s0);
             B.nslots = B.ntiles * B.ns * PLAN_TILE_SLOTS;
+            B.nrays = B.nslots * R.fan;
             R.batches.push_back(B);
         }
     return R;

@@ -243,4 +243,74 @@ DEV void smp_next2D(const DevSampler &S, PathSampler &p, uint32_t seed, uint64_t
     p.n2++;
 }
 
+// ---------------------------------------------------------------------------
+// Sample arrays (Sampler::request2DArray / next2DArray, sampler.cpp:61-117):
+// the `direct` and `ao` integrators request one 2D array per technique with
+// more than one sample (configureSampler: emitter array, then BSDF array).
+// Element k of request r of sample s is, like every draw, a pure function of
+// (pixel, s, r, k); the `path` kernels request none and never get here.
+//   independent  counter draws in dimensions kArrayDim | r << 24 | 2k (+ 1):
+//                bit 31 is set, which no regular dimension reaches
+//   halton       the sequence point offset + stride * (s n + k) in dimensions
+//                (5 + 2r, 6 + 2r), scrambled like the regular ones
+//                (halton.cpp:274-326)
+//   sobol        sample(look_up(s n + k), 5 + 2r / 6 + 2r) (sobol.cpp:171-198)
+//   ldsampler    per pixel and request spp * n scrambled (0,2) points in
+//                shuffled order, entry s n + k (ldsampler.cpp:162-195); scramble
+//                and shuffle come from the counter RNG: ld_shuffle on the next
+//                power of two, cycle-walked into [0, spp * n)
+//   hammersley   refuses arrays (hammersley.cpp:293-300): a load error
+// ---------------------------------------------------------------------------
+struct DevArrays {
+    uint32_t count;                // 2D array requests of the integrator (0..2)
+    uint32_t n[2];                 // their sizes, in request order
+};
+constexpr uint32_t kArrayStartDim = 5;           // m_arrayStartDim (halton.cpp:276, sobol.cpp:176)
+constexpr uint32_t kArrayDim = 0x80000000u;      // independent: the arrays' own dimension range
+constexpr uint64_t kLdArraySalt = 0x6172726179ull << 8;   // ldsampler: keys of the array requests
+
+// Regular draws of halton / sobol skip the dimensions reserved to arrays
+// (the tests at the top of next1D / next2D, halton.cpp:352-367, sobol.cpp:
+// 218-235); width: 1 (next1D) or 2 (next2D).  Without a request nothing is
+// reserved and the regular dimensions are those of `path`.
+template <int KIND>
+DEV void smp_skip_arrays(PathSampler &p, uint32_t nArrays, uint32_t width) {
+    if ((KIND == MTSG_SAMPLER_HALTON || KIND == MTSG_SAMPLER_SOBOL) && nArrays) {
+        const uint32_t end = kArrayStartDim + 2 * nArrays;
+        if (p.dim + (width - 1) >= kArrayStartDim && p.dim < end) p.dim = end;
+    }
+}
+
+template <int KIND>
+DEV void smp_array2D(const DevSampler &S, const PathSampler &p, uint32_t seed, uint64_t pixelIndex, uint32_t spp, uint32_t r,
+                     uint32_t n, uint32_t k, float &a, float &b) {
+    const uint64_t j = (uint64_t)p.s * n + k;
+    const uint32_t dim = kArrayStartDim + 2 * r;
+    if (KIND == MTSG_SAMPLER_SOBOL) {
+        const uint64_t idx = sobol_index(S, (uint32_t)j, p.x, p.y);
+        a = sobol_sample(S, idx, dim);
+        b = sobol_sample(S, idx, dim + 1);
+        return;
+    }
+    if (KIND == MTSG_SAMPLER_HALTON) {
+        const uint64_t idx = qmc_pixel_offset(S, p.x, p.y, spp) + (uint64_t)S.stride * j;
+        a = radical_inverse(S.primes[dim], idx, S.perm ? S.perm + S.off[dim] : nullptr);
+        b = radical_inverse(S.primes[dim + 1], idx, S.perm ? S.perm + S.off[dim + 1] : nullptr);
+        return;
+    }
+    if (KIND == MTSG_SAMPLER_LDSAMPLER) {
+        const uint64_t h = mix64(counterKey(seed ^ kLdSalt, pixelIndex) + (kLdArraySalt + r) * 0xD1B54A32D192ED03ULL);
+        const uint64_t sc = mix64(h ^ 0x5851F42D4C957F2DULL);
+        const uint32_t total = spp * n;   // <= 2^31 (mtsg.hip validate)
+        const uint32_t bits = total > 1u ? 32u - (uint32_t)__builtin_clz(total - 1u) : 0u;
+        uint32_t i = (uint32_t)j;
+        do i = ld_shuffle(i, bits, h); while (i >= total);   // a bijection of [0, 2^bits) walked back into [0, total)
+        a = radical_inverse2_single(i, (uint32_t)sc);
+        b = sobol2_single(i, (uint32_t)(sc >> 32));
+        return;
+    }
+    a = counterFloat(p.key, kArrayDim | (r << 24) | (2 * k));
+    b = counterFloat(p.key, kArrayDim | (r << 24) | (2 * k + 1));
+}
+
 }  // namespace mtsg

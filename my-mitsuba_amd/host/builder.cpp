@@ -770,8 +770,34 @@ void SceneBuilder::integrator(const std::string &type, const Properties &props, 
     }
     const std::string t = lower(type);
     if (t == "multichannel") { multichannel(props, line); return; }
+    if (t == "direct") {
+        // MIDirectIntegrator(props) (direct.cpp:93-108): shadingSamples is the
+        // shorthand for both counts
+        ip = IntegratorProps();
+        ip.type = t;
+        const int64_t shading = props.getInt("shadingSamples", 1);
+        const int64_t ne = props.getInt("emitterSamples", shading), nb = props.getInt("bsdfSamples", shading);
+        ip.strictNormals = props.getBool("strictNormals", false);
+        ip.hideEmitters = props.getBool("hideEmitters", false);
+        if (ne < 0 || nb < 0 || ne + nb > (int64_t)65536) throw err(at(line) + "direct: 'emitterSamples' and 'bsdfSamples' must lie in [0, 65536] together");
+        if (ne + nb == 0) throw err(at(line) + "direct: 'emitterSamples' + 'bsdfSamples' must be greater than zero (Assert(m_emitterSamples + m_bsdfSamples > 0))");
+        ip.emitterSamples = (int)ne;
+        ip.bsdfSamples = (int)nb;
+        return;
+    }
+    if (t == "ao") {
+        // AmbientOcclusionIntegrator(props) (ao.cpp:46-49)
+        ip = IntegratorProps();
+        ip.type = t;
+        const int64_t n = props.getInt("shadingSamples", 1);
+        if (n < 1 || n > (int64_t)65536) throw err(at(line) + "ao: 'shadingSamples' must lie in [1, 65536]");
+        ip.aoSamples = (int)n;
+        ip.aoRayLength = props.getFloat("rayLength", -1.0f);
+        if (ip.aoRayLength == 0) throw err(at(line) + "ao: 'rayLength' must not be zero");
+        return;
+    }
     if (t != "path")
-        throw err(at(line) + "integrator \"" + t + "\" is outside this build's scope (only 'path', 'multichannel' and 'myPath2_OM')");
+        throw err(at(line) + "integrator \"" + t + "\" is outside this build's scope (only 'path', 'direct', 'ao', 'multichannel' and 'myPath2_OM')");
     // MonteCarloIntegrator(props) (integrator.cpp:199-234)
     ip = IntegratorProps();
     ip.type = t;
@@ -812,6 +838,7 @@ int SceneBuilder::integratorChild(const std::string &type, const Properties &pro
     } else if (t == "multichannel") {
         throw err(at(line) + "multichannel: a nested 'multichannel' integrator is not supported");
     } else {
+        // (`direct` and `ao` included: the children share one sampler stream, see DESIGN)
         throw err(at(line) + "multichannel: child integrator \"" + t + "\" is outside this build's scope (only 'path' and 'field')");
     }
     if (pendingChildren.size() >= MTSG_MAX_SUBINTEGRATORS)
@@ -993,12 +1020,14 @@ void SceneBuilder::finish(const mtsh_scene_overrides *ov) {
         }
         if (ov->mask & MTSH_OVERRIDE_INTEGRATOR) {
             IntegratorProps &ip = scene.integrator;
-            if (ip.type != "path") throw err("integrator overrides apply to the `path` integrator");
-            // MonteCarloIntegrator's own checks (integrator.cpp:184-196)
-            if (ov->rr_depth <= 0) throw err("'rrDepth' must be set to a value greater than zero!");
-            if (ov->max_depth <= 0 && ov->max_depth != -1) throw err("'maxDepth' must be set to -1 (infinite) or a value greater than zero!");
-            ip.maxDepth = ov->max_depth;
-            ip.rrDepth = ov->rr_depth;
+            if (ip.type != "path" && ip.type != "direct") throw err("integrator overrides apply to the `path` and `direct` integrators");
+            if (ip.type == "path") {
+                // MonteCarloIntegrator's own checks (integrator.cpp:184-196); `direct` has neither property
+                if (ov->rr_depth <= 0) throw err("'rrDepth' must be set to a value greater than zero!");
+                if (ov->max_depth <= 0 && ov->max_depth != -1) throw err("'maxDepth' must be set to -1 (infinite) or a value greater than zero!");
+                ip.maxDepth = ov->max_depth;
+                ip.rrDepth = ov->rr_depth;
+            }
             ip.strictNormals = ov->strict_normals != 0;
             ip.hideEmitters = ov->hide_emitters != 0;
         }
@@ -1013,8 +1042,39 @@ void SceneBuilder::finish(const mtsh_scene_overrides *ov) {
         throw err("the film's pixelFormat lists " + std::to_string(scene.film.pixelFormats.size()) +
                   " entries, but the integrator produces one channel set (use 'multichannel')");
     }
+    // HammersleySampler::request2DArray (hammersley.cpp:297-301), which
+    // configureSampler calls for a count above 1 (direct.cpp:138-144, ao.cpp:65-70)
+    {
+        const IntegratorProps &ip = scene.integrator;
+        const bool arrays = (ip.type == "direct" && (ip.emitterSamples > 1 || ip.bsdfSamples > 1)) || (ip.type == "ao" && ip.aoSamples > 1);
+        if (arrays && scene.sampler.type == MTSG_SAMPLER_HAMMERSLEY)
+            throw err("request2DArray(): Not supported for the Hammersley QMC sequence! If you used this sampler together with the "
+                      "'direct' or 'ao' integrators, you will have to set the 'shadingSamples' parameter to 1 to use this sampler.");
+    }
     scene.finalize();
     scene.buildAov();
+    scene.buildDirect();
+}
+
+// The direct / ao descriptor beside the scene descriptor (mtsg.h
+// mtsg_direct_desc); ao's default ray length is half the radius of the scene's
+// bounding sphere (AmbientOcclusionIntegrator::preprocess, ao.cpp:72-82)
+void Scene::buildDirect() {
+    memset(&directDesc, 0, sizeof(directDesc));
+    if (integrator.type == "direct") {
+        directDesc.emitter_samples = (uint32_t)integrator.emitterSamples;
+        directDesc.bsdf_samples = (uint32_t)integrator.bsdfSamples;
+    } else if (integrator.type == "ao") {
+        directDesc.ao_samples = (uint32_t)integrator.aoSamples;
+        float len = integrator.aoRayLength;
+        if (len < 0) {
+            const float camPos[3] = {camera.camera_to_world[3], camera.camera_to_world[7], camera.camera_to_world[11]};
+            float center[3], radius;
+            sceneBoundingSphere(desc.aabb_min, desc.aabb_max, camPos, center, radius);
+            len = radius * 0.5f;
+        }
+        directDesc.ao_ray_length = len;
+    }
 }
 
 // The multichannel descriptor beside the scene descriptor (mtsg.h

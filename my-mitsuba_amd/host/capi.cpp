@@ -286,6 +286,14 @@ const mtsg_aov_desc *mtsh_scene_aov(const mtsh_scene *s) {
     return s && s->scene->integrator.multichannel ? &s->scene->aovDesc : nullptr;
 }
 
+int mtsh_scene_direct(const mtsh_scene *s, mtsg_direct_desc *out) {
+    if (!s) return 0;
+    const std::string &t = s->scene->integrator.type;
+    if (t != "direct" && t != "ao") return 0;
+    if (out) *out = s->scene->directDesc;
+    return 1;
+}
+
 int mtsh_scene_film_formats(const mtsh_scene *s, int32_t *formats, int capacity) {
     try {
         std::vector<std::string> ch;
@@ -333,7 +341,9 @@ void mtsh_scene_render_params(const mtsh_scene *s, mtsg_render_params *p) {
     p->tile_h = sc.film.cropH;
     p->tile_stride = 1;
     p->tile_offset = 0;
-    p->integrator = sc.integrator.type == "myPath2_OM" ? MTSG_INTEGRATOR_PATH2_OM : MTSG_INTEGRATOR_PATH;
+    const std::string &it = sc.integrator.type;
+    p->integrator = it == "myPath2_OM" ? MTSG_INTEGRATOR_PATH2_OM : it == "direct" ? MTSG_INTEGRATOR_DIRECT : it == "ao" ? MTSG_INTEGRATOR_AO
+                                                                                                                        : MTSG_INTEGRATOR_PATH;
     p->om_strategy = sc.integrator.omStrategy;
     p->om_mis = sc.integrator.omMis;
     p->om_jitter = sc.integrator.omJitter ? 1 : 0;

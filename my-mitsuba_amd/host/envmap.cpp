@@ -21,6 +21,17 @@ inline float luminance(float r, float g, float b) { return r * 0.212671f + g * 0
 
 }  // namespace
 
+void sceneBoundingSphere(const float aabbMin[3], const float aabbMax[3], const float camPos[3], float center[3], float &radius) {
+    float mn[3], mx[3];
+    for (int k = 0; k < 3; ++k) {
+        mn[k] = std::min(aabbMin[k], camPos[k]);
+        mx[k] = std::max(aabbMax[k], camPos[k]);
+        center[k] = (mn[k] + mx[k]) * 0.5f;
+    }
+    const float dx = center[0] - mx[0], dy = center[1] - mx[1], dz = center[2] - mx[2];
+    radius = std::sqrt(dx * dx + dy * dy + dz * dz);
+}
+
 void buildEnvmap(const Emitter &e, const float aabbMin[3], const float aabbMax[3], const float camPos[3],
                  std::vector<float> &texels, std::vector<float> &cdfRows, std::vector<float> &cdfCols,
                  std::vector<float> &rowWeights, mtsg_envmap &env) {
@@ -71,14 +82,8 @@ void buildEnvmap(const Emitter &e, const float aabbMin[3], const float aabbMax[3
             env.to_local[3 * r + c] = e.toWorld.inv[r][c];
         }
     // scene bounding sphere x 1.5
-    float mn[3], mx[3], center[3];
-    for (int k = 0; k < 3; ++k) {
-        mn[k] = std::min(aabbMin[k], camPos[k]);
-        mx[k] = std::max(aabbMax[k], camPos[k]);
-        center[k] = (mn[k] + mx[k]) * 0.5f;
-    }
-    const float dx = center[0] - mx[0], dy = center[1] - mx[1], dz = center[2] - mx[2];
-    const float radius = std::sqrt(dx * dx + dy * dy + dz * dz);
+    float center[3], radius;
+    sceneBoundingSphere(aabbMin, aabbMax, camPos, center, radius);
     for (int k = 0; k < 3; ++k) env.bsphere_center[k] = center[k];
     env.bsphere_radius = std::max(1e-4f, radius * 1.5f);
 }

@@ -1,5 +1,6 @@
 // mtsg-render: command-line front end mirroring `mitsuba scene.xml`
-// (src/mitsuba/mitsuba.cpp:154-418) for the `path` integrator on MI355X:
+// (src/mitsuba/mitsuba.cpp:154-418) for the `path`, `direct` and `ao`
+// integrators on MI355X:
 //   mtsg-render [-D name=value]... [-o out.pfm] [-g gpus] scene.xml
 // A scene whose integrator is `multichannel` is written as OpenEXR (hdrfilm's
 // multichannel output, hdrfilm.cpp:328-334; default out.exr), one FLOAT

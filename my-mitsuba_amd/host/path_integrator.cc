@@ -155,6 +155,16 @@ int mtsh_path_job_create(const mtsh_scene *scene, int n_gpus, mtsh_path_job **ou
             }
             job->multiChannels = 3 * (int)aov->n_children + 2;
         }
+        // a direct / ao scene: its sample counts on every GPU
+        mtsg_direct_desc dd;
+        if (mtsh_scene_direct(scene, &dd)) {
+            const int rcd = mtsg_scene_set_direct(job->handles[g], &dd);
+            if (rcd != MTSG_OK) {
+                g_perr = "GPU " + std::to_string(g) + ": " + device_error();
+                mtsh_path_job_destroy(job);
+                return rcd;
+            }
+        }
     }
     *out = job;
     return MTSG_OK;

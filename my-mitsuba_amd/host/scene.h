@@ -133,6 +133,11 @@ struct IntegratorProps {
     bool multichannel = false;
     struct Child { int kind; V3 undefined; };   // MTSG_AOV_PATH / MTSG_FIELD_*
     std::vector<Child> children;
+    // direct (direct.cpp:93-108) and ao (ao.cpp:46-49); aoRayLength < 0: half
+    // the radius of the scene's bounding sphere (ao.cpp:77-80), resolved by
+    // Scene::buildDirect
+    int emitterSamples = 1, bsdfSamples = 1, aoSamples = 1;
+    float aoRayLength = -1.0f;
 };
 
 struct KDBuildParams {                // gkdtree.h:734-744 defaults, except stopPrims
@@ -214,6 +219,9 @@ struct Scene {
     std::vector<uint32_t> aovElems;
     mtsg_aov_desc aovDesc{};
     void buildAov();
+    // direct / ao scenes (buildDirect): the descriptor beside `desc`
+    mtsg_direct_desc directDesc{};
+    void buildDirect();
 
     std::vector<uint8_t> triGrouped;  // triangle lives in a shape group's own tree (two-level)
 
@@ -225,6 +233,11 @@ struct Scene {
 
 extern int g_defaultKDThreads;   // 0 = hardware concurrency
 extern int g_instancing;         // MTSH_INSTANCING_* of the next load
+
+// Scene::getAABB().getBSphere() (scene.cpp:412-440, aabb.h getBSphere): the
+// kd-tree AABB expanded by the sensor position, and the sphere around its
+// centre through its maximum corner
+void sceneBoundingSphere(const float aabbMin[3], const float aabbMax[3], const float camPos[3], float center[3], float &radius);
 
 // Environment emitter tables (envmap.cpp in this directory)
 void buildEnvmap(const Emitter &e, const float aabbMin[3], const float aabbMax[3], const float camPos[3],

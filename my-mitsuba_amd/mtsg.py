@@ -35,6 +35,11 @@ MTSG_OPT_STAGGER = 4
 MTSG_OPT_SHADE_GENERIC = 5
 MTSG_OPT_RAY_ORDER = 6
 MTSG_OPT_CAMERA_DIFFS = 7
+# mtsg_render_params.integrator
+MTSG_INTEGRATOR_PATH = 0
+MTSG_INTEGRATOR_PATH2_OM = 1
+MTSG_INTEGRATOR_DIRECT = 2
+MTSG_INTEGRATOR_AO = 3
 
 
 class RenderParams(C.Structure):
@@ -276,6 +281,12 @@ class Aov:
                          C.string_at(d.elem_starts, 4 * d.n_elems) if d.n_elems else b""])
 
 
+class DirectDesc(C.Structure):
+    """mtsg_direct_desc (include/mtsg.h): the sample counts of `direct` and `ao`."""
+    _fields_ = [("emitter_samples", C.c_uint32), ("bsdf_samples", C.c_uint32), ("ao_samples", C.c_uint32),
+                ("ao_ray_length", C.c_float)]
+
+
 class DigestEntry(C.Structure):
     """mtsh_digest_entry."""
     _fields_ = [("name", C.c_char * 32), ("bytes", C.c_uint64), ("hash", C.c_uint64)]
@@ -297,7 +308,7 @@ DEVICE_SYMBOLS = [
     "mtsg_sampler_draws", "mtsg_debug_wavetimes", "mtsg_set_tile_callback",
     "mtsg_debug_stragglers", "mtsg_set_test_knobs", "mtsg_set_option",
     "mtsg_scene_set_aov", "mtsg_render_multi", "mtsg_render_device_multi", "mtsg_render_device_tiles_multi",
-    "mtsg_render_samples_multi",
+    "mtsg_render_samples_multi", "mtsg_scene_set_direct",
 ]
 HOST_SYMBOLS = [
     "mtsh_scene_load", "mtsh_scene_load_overrides", "mtsh_scene_load_props", "mtsh_scene_set_scene_props", "mtsh_set_kd_threads", "mtsh_set_instancing", "mtsh_scene_desc", "mtsh_scene_render_params",
@@ -308,7 +319,7 @@ HOST_SYMBOLS = [
     "mtsh_scene_add_shape", "mtsh_scene_add_mesh", "mtsh_scene_add_instance", "mtsh_scene_set_sensor", "mtsh_scene_set_film",
     "mtsh_scene_set_sampler", "mtsh_scene_set_integrator", "mtsh_scene_finish", "mtsh_scene_abort", "mtsh_scene_digest",
     "mtsh_scene_add_integrator_child", "mtsh_scene_set_multichannel", "mtsh_scene_aov", "mtsh_scene_film_formats",
-    "mtsh_scene_film_channels", "mtsh_develop_multi", "mtsh_write_exr",
+    "mtsh_scene_film_channels", "mtsh_develop_multi", "mtsh_write_exr", "mtsh_scene_direct",
 ]
 PATH_SYMBOLS = [
     "mtsh_path_job_create", "mtsh_path_job_gpus", "mtsh_path_job_render", "mtsh_path_job_cancel",
@@ -417,6 +428,8 @@ def host_lib() -> C.CDLL:
         lib.mtsh_scene_set_multichannel.argtypes = [C.c_void_p, PP, C.c_int32]
         lib.mtsh_scene_aov.restype = C.POINTER(AovDesc)
         lib.mtsh_scene_aov.argtypes = [C.c_void_p]
+        lib.mtsh_scene_direct.restype = C.c_int
+        lib.mtsh_scene_direct.argtypes = [C.c_void_p, C.POINTER(DirectDesc)]
         lib.mtsh_scene_film_formats.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
         lib.mtsh_scene_film_channels.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.mtsh_develop_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p]
@@ -462,6 +475,7 @@ def device_lib() -> C.CDLL:
         lib.mtsg_trace_shadow.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.mtsg_render_samples.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p]
         lib.mtsg_scene_set_aov.argtypes = [C.c_void_p, C.POINTER(AovDesc)]
+        lib.mtsg_scene_set_direct.argtypes = [C.c_void_p, C.POINTER(DirectDesc)]
         for fn in ("mtsg_render_multi", "mtsg_render_device_multi", "mtsg_render_device_tiles_multi",
                    "mtsg_render_samples_multi"):
             getattr(lib, fn).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p]
@@ -604,6 +618,11 @@ class Scene:
         """The multichannel child set (mtsh_scene_aov), None for plain scenes."""
         d = host_lib().mtsh_scene_aov(self._h)
         return Aov(self, d) if d else None
+
+    def direct(self) -> "DirectDesc | None":
+        """The sample counts of a `direct` or `ao` scene (mtsh_scene_direct), None for other integrators."""
+        d = DirectDesc()
+        return d if host_lib().mtsh_scene_direct(self._h, C.byref(d)) else None
 
     def textures(self) -> list:
         """The scene's bitmap texture headers (TextureHeader)."""
@@ -953,6 +972,14 @@ class GPUScene:
         # a multichannel scene's child set is part of the scene
         if getattr(scene, "aov", None) is not None and scene.aov() is not None:
             self.set_aov(scene)
+        # ... and so are the sample counts of a direct / ao scene
+        if getattr(scene, "direct", None) is not None and scene.direct() is not None:
+            self.set_direct(scene.direct())
+
+    def set_direct(self, desc: "DirectDesc | None") -> None:
+        """Give the handle the sample counts of `direct` / `ao` renders (mtsg_scene_set_direct); None removes them."""
+        self._check(device_lib().mtsg_scene_set_direct(self._h, C.byref(desc) if desc is not None else None),
+                    "mtsg_scene_set_direct")
 
     def set_aov(self, scene: "Scene | None") -> None:
         """Activate the multichannel child set of `scene` (mtsg_scene_set_aov); None turns it off."""
@@ -1064,9 +1091,10 @@ class GPUScene:
 
     def sampler_draws(self, params: RenderParams, x: int, y: int, s: int, kinds) -> np.ndarray:
         """The scene sampler's next1D (kind 1) / next2D (kind 2) draws of one
-        sample, flattened (debug entry point)."""
+        sample, flattened (debug entry point); kind -n is next2DArray(n), 2n
+        floats, for the arrays the handle's direct / ao descriptor requests."""
         kinds = np.ascontiguousarray(kinds, dtype=np.int32)
-        out = np.empty(int(np.where(kinds == 2, 2, 1).sum()), np.float32)
+        out = np.empty(int(np.where(kinds < 0, -2 * kinds, np.where(kinds == 2, 2, 1)).sum()), np.float32)
         self._check(device_lib().mtsg_sampler_draws(self._h, C.byref(params), x, y, s, kinds.size, _ptr(kinds), _ptr(out)),
                     "mtsg_sampler_draws")
         return out

@@ -5,6 +5,8 @@
 //   (b) a batch never exceeds a lane's share of the path budget,
 //   (c) the planned tile groups are a multiple of the lane count, or one per tile,
 //   (d) the single-lane modes and calls of fewer than two tiles take one lane,
+//   (e) a batch's fan (direct / ao: `fan` rays per path slot) is nslots * fan
+//       and stays within PLAN_MAX_RAYS, whatever the path budget,
 // then a few literal plans worked out by hand from the formulas (README's "C5
 // in three batches" among them).  `make` builds it with ASan + UBSan;
 // tests/test_render_plan.py runs it.
@@ -24,17 +26,18 @@ struct Case {
     int stride, offset;
     uint32_t keys, maxPaths, lanes;
     bool single;
+    uint32_t fan = 1;
 };
 
 [[noreturn]] void fail(const Case &c, const char *what) {
-    fprintf(stderr, "check_render_plan: FAILED %s at %dx%d spp %u stride %d offset %d keys %u maxPaths %u lanes %u single %d\n", what,
-            c.w, c.h, c.spp, c.stride, c.offset, c.keys, c.maxPaths, c.lanes, (int)c.single);
+    fprintf(stderr, "check_render_plan: FAILED %s at %dx%d spp %u stride %d offset %d keys %u maxPaths %u lanes %u single %d fan %u\n", what,
+            c.w, c.h, c.spp, c.stride, c.offset, c.keys, c.maxPaths, c.lanes, (int)c.single, c.fan);
     exit(1);
 }
 #define CHECK(c, cond) do { if (!(cond)) fail(c, #cond); } while (0)
 
 RenderPlan plan_of(const Case &c) {
-    return plan_render(c.w, c.h, c.spp, c.stride, c.offset, c.keys, c.maxPaths, c.lanes, c.single);
+    return plan_render(c.w, c.h, c.spp, c.stride, c.offset, c.keys, c.maxPaths, c.lanes, c.single, c.fan);
 }
 
 // the invariants (a)-(d) of one plan
@@ -51,7 +54,8 @@ RenderPlan check(const Case &c) {
     // (d)
     CHECK(c, R.lanes == ((c.single || R.ntiles < 2) ? 1u : c.lanes));
     // (b)
-    const uint64_t lanePaths = std::max<uint64_t>(256, c.maxPaths / R.lanes);
+    const uint64_t lanePaths = std::max<uint64_t>(256, std::min<uint64_t>(c.maxPaths / R.lanes, (1ull << 31) / c.fan));
+    CHECK(c, R.fan == c.fan);
     CHECK(c, R.sppPerBatch >= 1 && R.tilesPerBatch >= 1);
     CHECK(c, (uint64_t)R.tilesPerBatch * R.sppPerBatch * 256 <= lanePaths);
     // (a), and the order: tile-major, then sample-major
@@ -62,6 +66,8 @@ RenderPlan check(const Case &c) {
         CHECK(c, B.ntiles >= 1 && B.ns >= 1 && (uint64_t)B.tile0 + B.ntiles <= R.ntiles && (uint64_t)B.s0 + B.ns <= c.spp);
         CHECK(c, B.ntiles <= R.tilesPerBatch && B.ns <= R.sppPerBatch);
         CHECK(c, (uint64_t)B.nslots == (uint64_t)B.ntiles * B.ns * 256 && B.nslots <= lanePaths);
+        // (e)
+        CHECK(c, (uint64_t)B.nrays == (uint64_t)B.nslots * c.fan && (uint64_t)B.nslots * c.fan <= (1ull << 31));
         if (B.s0 == 0) ++groups;
         if (i) {
             const PlanBatch &A = R.batches[i - 1];
@@ -92,6 +98,17 @@ void sweep() {
                                 check(Case{r[0], r[1], spp, stride, offset, 0, mp, lanes, single != 0});
                         for (uint32_t keys : {1u, 2u, 7u}) check(Case{r[0], r[1], spp, 0, 0, keys, mp, lanes, single != 0});
                     }
+    // the fan of direct / ao renders (one lane): 2 = (1,1), 8 = (4,4), an odd
+    // one, one that caps the default budget, and the largest
+    for (auto &r : rects)
+        for (uint32_t spp : spps)
+            for (uint32_t mp : paths)
+                for (uint32_t fan : {2u, 8u, 13u, 1000u, PLAN_MAX_FAN}) {
+                    for (int stride = 0; stride <= 3; ++stride)
+                        for (int offset = 0; offset < std::max(1, stride); ++offset)
+                            check(Case{r[0], r[1], spp, stride, offset, 0, mp, 1, true, fan});
+                    check(Case{r[0], r[1], spp, 0, 0, 7, mp, 1, true, fan});
+                }
 }
 
 void literals() {
@@ -122,6 +139,21 @@ void literals() {
         const Case c{100, 40, 4, 3, 1, 0, dflt, 1, false};
         const RenderPlan R = check(c);
         CHECK(c, R.tilesX == 7 && R.allTiles == 21 && R.ntiles == 7 && R.batches.size() == 1 && R.batches[0].nslots == 7168);
+    }
+    {   // direct (4,4) at 1280x720, 64 spp: 8 rays per slot cap a batch at 2^28 slots, so one batch still
+        const Case c{1280, 720, 64, 0, 0, 0, dflt, 1, true, 8};
+        const RenderPlan R = check(c);
+        CHECK(c, R.batches.size() == 1 && R.batches[0].nslots == 58982400u && R.batches[0].nrays == 471859200u);
+    }
+    {   // a fan of 1000 over 200x120, 64 spp: 2^31 / 1000 = 2147483 slots per batch hold 131 tiles of 64 samples
+        const Case c{200, 120, 64, 0, 0, 0, dflt, 1, true, 1000};
+        const RenderPlan R = check(c);
+        CHECK(c, R.ntiles == 104 && R.sppPerBatch == 64 && R.tilesPerBatch == 104 && R.batches.size() == 1);
+    }
+    {   // the same at 640x480: 1200 tiles in ten groups of 120
+        const Case c{640, 480, 64, 0, 0, 0, dflt, 1, true, 1000};
+        const RenderPlan R = check(c);
+        CHECK(c, R.ntiles == 1200 && R.tilesPerBatch == 120 && R.batches.size() == 10 && R.batches[0].nrays == 1966080000u);
     }
     {   // two tiles keep the lanes asked for; the groups stop at one per tile
         const Case c{32, 16, 1, 0, 0, 0, dflt, 4, false};
