@@ -949,6 +949,18 @@ DEV uint2 spec_take(SpecRay &r, const uint4 &pr, float tsplit, bool goLeft, bool
 #define MTSG_TIE_INLINE 0   // measured r06: C3 trace +4.4 ms (64 VGPRs at the 8-wave limit), C2 +6.4 ms, C5 +40 ms: off
 #endif
 constexpr bool TIE_INLINE = MTSG_TIE_INLINE;
+// k_trace_s: a finished ray's bookkeeping (tie-list entry, error flag, miss
+// record or unoccluded shadow contribution) waits until its wave refills
+// instead of running in the iteration that finished it -- with ~50 busy lanes
+// and a ray living ~22 iterations, nine in ten iterations ran that tail for
+// one or two lanes, load chain of shadow_unoccluded included (round 7).
+// 0: in the iteration, as through round 6.  The same records from the same
+// lanes, later in the same launch.  Measured r07: C3 trace 113.96 -> 110.35 ms
+// (SQ_WAIT_ANY per wave -10%, VALU -1.1%; profiles/r07_retire_ab.txt).
+#ifndef MTSG_RETIRE_BATCH
+#define MTSG_RETIRE_BATCH 1
+#endif
+constexpr bool RETIRE_BATCH = MTSG_RETIRE_BATCH;
 __shared__ uint32_t s_mbPrev[TRACE_BLOCK];
 // the tie branch of mailbox_step (mb: the state before this test)
 DEV bool mailbox_tie(SpecRay &r, uint32_t mb, uint32_t sl, uint32_t id, const float4 *hitOut) {
@@ -1865,9 +1877,10 @@ DEV uint32_t shuffle_index(uint32_t x, uint32_t n) {
     return x;
 }
 
-template <bool COUNT, int MIN_IDLE, bool INST = false, bool KNOBS = false>
-__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(INST ? (COUNT ? 1 : MTSG_INST_WAVES) : MTSG_SPEC_WAVES)))
-k_trace_s(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned long long *wt) {
+// (the kernel's body: k_trace_s below, and under MTSG_FLAT_REGS its flat
+// specialisations with their own register budget in trace_flat.hip)
+template <bool COUNT, int MIN_IDLE, bool INST, bool KNOBS>
+DEV void trace_s_body(const DevScene &S, const DevPaths &P, int cIn, int sIn, uint32_t nIdentity, unsigned long long *wt) {
     const SpecStack stk{};
     const TravLimits L = trav_limits<KNOBS>(S);
     lds_top_init(S);
@@ -1887,9 +1900,64 @@ k_trace_s(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned
     unsigned long long tExh = 0;           // wt: when the work list was found empty
     uint32_t drainIters = 0;               // wt: loop iterations after that
     SpecRay r;
+    // RETIRE_BATCH: the lane's finished ray waits for retire().  A lane mask in
+    // an SGPR pair, no VGPR (61 as before); under the 78-SGPR budget it costs
+    // two more SGPR spills (sgpr_spill_count 20 -> 22, v_readlane / v_writelane
+    // in the kernel 46 -> 52), included in the measured gain
+    bool pend = false;
+    // What a finished ray leaves behind besides the hits written through: its
+    // entry in the tie list, the error flag, the miss record or the unoccluded
+    // shadow ray's contribution (and the COUNT pass's per-ray figures).  Reads
+    // only the lane's idx / r / iters, which stay as the ray left them until
+    // the lane's refill.
+    auto retire = [&]() {
+        if (MTSG_MAILBOX && !(!INST && TIE_INLINE) && (r.bits & (SB_TIE | SB_SHADOW | SB_MBRUN)) == SB_TIE) {
+            if (COUNT) atomicAdd(&P.ctr[CTR_TIE_RETRACES], 1ull);
+            // k_tie / k_tie_i trace it again with the mailboxes
+            P.tie[atomicAdd(&P.cnt[CNT_TIE], 1u)] = idx;
+        }
+        if (COUNT) {
+            const bool sh = (r.bits & SB_SHADOW) != 0;
+            if (!INST) {
+                // kd-restarts of the ray, and those that took the guard's
+                // one-ulp step (restart number >= rstGuard, kd_restart)
+                const uint32_t nr = (r.bits >> SB_RST_SHIFT) & SB_RST_MASK;
+                if (nr) atomicAdd(&P.ctr[CTR_RESTARTS + sh], (unsigned long long)nr);
+                if (nr > L.rstGuard) {
+                    atomicAdd(&P.ctr[CTR_GUARD_RAYS + sh], 1ull);
+                    atomicAdd(&P.ctr[CTR_GUARD_STEPS + sh], (unsigned long long)(nr - L.rstGuard));
+                }
+            }
+            atomicMax(&P.ctr[sh ? CTR_SHADOW + CTR_ITER_MAX : CTR_ITER_MAX], (unsigned long long)iters);
+            atomicAdd(&P.ctr[(sh ? CTR_HIST_SHADOW : CTR_HIST_CLOSEST) + min(CTR_HIST_BINS - 1, 31 - __clz(max(iters, 1u)))], 1ull);
+            if (iters >= STRAGGLER_ITERS) {
+                const unsigned long long k = atomicAdd(&P.ctr[CTR_STRAGGLERS], 1ull);
+                if (k < STRAGGLER_MAX) {
+                    unsigned long long *o = P.ctr + CTR_STRAGGLER_RECORDS + CTR_STRAGGLER_WORDS * k;
+                    o[0] = __float_as_uint(r.o.x); o[1] = __float_as_uint(r.o.y); o[2] = __float_as_uint(r.o.z);
+                    o[3] = __float_as_uint(r.d.x); o[4] = __float_as_uint(r.d.y); o[5] = __float_as_uint(r.d.z);
+                    const TraceCounts &kk = sh ? cs : cc;
+                    o[6] = iters | (sh ? 0x80000000u : 0u);
+                    o[7] = min(kk.nodes - n0, 4095u) | min(kk.tests - t0c, 4095u) << 12 | min(kk.restarts - r0, 255u) << 24;
+                }
+            }
+        }
+        if (r.bits & SB_ERR) atomicOr(&P.cnt[CNT_ERR], CNT_ERR_TRAVERSAL);
+        // closest: hits were written through, only a miss needs a record
+        if (!(r.bits & SB_FOUND)) {
+            if (r.bits & SB_SHADOW) shadow_unoccluded(P, idx);
+            else stS(&P.hit[idx], miss_record());
+        }
+    };
     for (;;) {
         unsigned long long idle = __ballot(!active);
         if ((uint32_t)__popcll(idle) < (uint32_t)MIN_IDLE && __any(active)) idle = 0;
+        // the wave is about to refill (or has run dry): retire every finished
+        // ray at once, before the refill overwrites idx / r
+        if (RETIRE_BATCH && idle && pend) {
+            retire();
+            pend = false;
+        }
         while (idle && !exhausted) {
             if (poolLeft == 0 && !F.next(FETCH, poolBase, poolLeft)) {
                 exhausted = true;
@@ -1963,56 +2031,21 @@ k_trace_s(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned
             }
         }
         if (COUNT && active) ++iters;
-        if (done && MTSG_MAILBOX && (r.bits & (SB_TIE | SB_SHADOW | SB_MBRUN)) == SB_TIE) {
+        if (done && MTSG_MAILBOX && !INST && TIE_INLINE && (r.bits & (SB_TIE | SB_SHADOW | SB_MBRUN)) == SB_TIE) {
+            // a closest ray that met an exact tie is traced again from its
+            // start in this lane with the mailbox (tie_retrace), inside the
+            // launch: its drain absorbs the retrace, no k_tie launch follows
             if (COUNT) atomicAdd(&P.ctr[CTR_TIE_RETRACES], 1ull);
-            if (!INST && TIE_INLINE) {
-                // a closest ray that met an exact tie is traced again from its
-                // start in this lane with the mailbox (tie_retrace), inside the
-                // launch: its drain absorbs the retrace, no k_tie launch follows
-                float4 ro, rd;
-                load_closest_ray(S, P, idx, P.camEnc != 0, ro, rd);
-                spec_init(S, xyz(ro), xyz(rd), ro.w, rd.w, false, r);   // true: it passed before
-                r.bits |= SB_MBRUN;
-                done = false;
-            } else {
-                // k_tie_i traces it again with the two-level mailboxes
-                P.tie[atomicAdd(&P.cnt[CNT_TIE], 1u)] = idx;
-            }
+            float4 ro, rd;
+            load_closest_ray(S, P, idx, P.camEnc != 0, ro, rd);
+            spec_init(S, xyz(ro), xyz(rd), ro.w, rd.w, false, r);   // true: it passed before
+            r.bits |= SB_MBRUN;
+            done = false;
         }
         if (done) {
             active = false;
-            if (COUNT) {
-                const bool sh = (r.bits & SB_SHADOW) != 0;
-                if (!INST) {
-                    // kd-restarts of the ray, and those that took the guard's
-                    // one-ulp step (restart number >= rstGuard, kd_restart)
-                    const uint32_t nr = (r.bits >> SB_RST_SHIFT) & SB_RST_MASK;
-                    if (nr) atomicAdd(&P.ctr[CTR_RESTARTS + sh], (unsigned long long)nr);
-                    if (nr > L.rstGuard) {
-                        atomicAdd(&P.ctr[CTR_GUARD_RAYS + sh], 1ull);
-                        atomicAdd(&P.ctr[CTR_GUARD_STEPS + sh], (unsigned long long)(nr - L.rstGuard));
-                    }
-                }
-                atomicMax(&P.ctr[sh ? CTR_SHADOW + CTR_ITER_MAX : CTR_ITER_MAX], (unsigned long long)iters);
-                atomicAdd(&P.ctr[(sh ? CTR_HIST_SHADOW : CTR_HIST_CLOSEST) + min(CTR_HIST_BINS - 1, 31 - __clz(max(iters, 1u)))], 1ull);
-                if (iters >= STRAGGLER_ITERS) {
-                    const unsigned long long k = atomicAdd(&P.ctr[CTR_STRAGGLERS], 1ull);
-                    if (k < STRAGGLER_MAX) {
-                        unsigned long long *o = P.ctr + CTR_STRAGGLER_RECORDS + CTR_STRAGGLER_WORDS * k;
-                        o[0] = __float_as_uint(r.o.x); o[1] = __float_as_uint(r.o.y); o[2] = __float_as_uint(r.o.z);
-                        o[3] = __float_as_uint(r.d.x); o[4] = __float_as_uint(r.d.y); o[5] = __float_as_uint(r.d.z);
-                        const TraceCounts &kk = sh ? cs : cc;
-                        o[6] = iters | (sh ? 0x80000000u : 0u);
-                        o[7] = min(kk.nodes - n0, 4095u) | min(kk.tests - t0c, 4095u) << 12 | min(kk.restarts - r0, 255u) << 24;
-                    }
-                }
-            }
-            if (r.bits & SB_ERR) atomicOr(&P.cnt[CNT_ERR], CNT_ERR_TRAVERSAL);
-            // closest: hits were written through, only a miss needs a record
-            if (!(r.bits & SB_FOUND)) {
-                if (r.bits & SB_SHADOW) shadow_unoccluded(P, idx);
-                else stS(&P.hit[idx], miss_record());
-            }
+            if (RETIRE_BATCH) pend = true;   // retired at the loop head, before the lane's refill
+            else retire();
         }
     }
     flush_counts<COUNT>(P.ctr, cc);
@@ -2030,6 +2063,36 @@ k_trace_s(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned
         wt[WT_WORDS * blockIdx.x + 2] = tExh;
         wt[WT_WORDS * blockIdx.x + 3] = drainIters;
     }
+}
+
+// Register budget of the flat production instantiations, a measurement
+// variant (MTSG_FLAT_REGS=1; their explicit specialisations are in
+// trace_flat.hip, the one unit that launches them).
+// amdgpu_waves_per_eu(8) makes the compiler budget 78 SGPRs (800 / 8 less the
+// trap handler's 16, rounded down to the allocation granule, less VCC), and
+// the kernel spills ~20 SGPRs into VGPR lanes.  Two figures are involved:
+// amdgpu_num_sgpr(N) is the compiler's budget and counts VCC with the
+// kernel's registers; the code object's sgpr_count, N - 2 here, is what the
+// occupancy query sees, and it rounds that up to the allocation step of 16
+// (800 SGPRs per SIMD: 96 -> 8 waves, 112 -> 7).  So the largest budget that
+// keeps 8 waves/SIMD is N = 98: sgpr_count 96, 8 SGPR spills (16 v_readlane /
+// v_writelane in the kernel), 64 VGPRs (from 61), the query still 32
+// workgroups per CU.  Measured (C3 trace ms, medians of 3 alternated runs,
+// session 1 of profiles/r07_retire_ab.txt): alone it loses, 115.84 against
+// the parent's 113.42; on top of MTSG_RETIRE_BATCH 109.78 against 109.81, no
+// difference.  Off.
+#ifndef MTSG_FLAT_REGS
+#define MTSG_FLAT_REGS 0
+#endif
+#ifndef MTSG_FLAT_SGPRS
+#define MTSG_FLAT_SGPRS 98
+#endif
+#define FLAT_TRACE_ATTR __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_num_vgpr(64), amdgpu_num_sgpr(MTSG_FLAT_SGPRS)))
+template <bool COUNT, int MIN_IDLE, bool INST = false, bool KNOBS = false>
+__global__ void __launch_bounds__(TRACE_BLOCK)
+__attribute__((amdgpu_waves_per_eu(INST ? (COUNT ? 1 : MTSG_INST_WAVES) : (MTSG_FLAT_REGS && !COUNT ? 0 : MTSG_SPEC_WAVES))))   // (0: no attribute)
+k_trace_s(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned long long *wt) {
+    trace_s_body<COUNT, MIN_IDLE, INST, KNOBS>(S, P, cIn, sIn, nIdentity, wt);
 }
 
 // ---------------------------------------------------------------------------

@@ -10,6 +10,24 @@
 #pragma clang diagnostic ignored "-Wunused-function"
 #include "kernels.h"
 
+#if MTSG_FLAT_REGS
+namespace {
+// measurement variant: the flat production kernels with their own register
+// budget (kernels.h FLAT_TRACE_ATTR, measured: off); the COUNT instantiations
+// keep the template's attributes
+#define FLAT_TRACE_KERNEL(MIN_IDLE, KNOBS)                                                                               \
+    template <>                                                                                                          \
+    __global__ void FLAT_TRACE_ATTR k_trace_s<false, MIN_IDLE, false, KNOBS>(DevScene S, DevPaths P, int cIn, int sIn,   \
+                                                                             uint32_t nIdentity, unsigned long long *wt) { \
+        trace_s_body<false, MIN_IDLE, false, KNOBS>(S, P, cIn, sIn, nIdentity, wt);                                      \
+    }
+FLAT_TRACE_KERNEL(16, false)
+FLAT_TRACE_KERNEL(32, false)
+FLAT_TRACE_KERNEL(16, true)
+#undef FLAT_TRACE_KERNEL
+}  // namespace
+#endif
+
 namespace mtsg {
 
 template <bool COUNT>

@@ -45,6 +45,11 @@ struct mtsh_path_job {
     std::vector<int> rendering, sent;
     std::vector<std::mutex> gpuLock;
     std::mutex renderLock;   // one render at a time per job
+    // a render call is in progress, from its entry to its return (under
+    // stateLock): cancel() counts from the entry on, whatever the call still
+    // does before its GPU threads start, and has no effect outside
+    std::mutex stateLock;
+    bool active = false;
     // tile completion: the caller's hook, serialised over the GPU threads
     mtsh_path_tile_fn tileFn = nullptr;
     void *tileUser = nullptr;
@@ -202,6 +207,17 @@ int job_render(mtsh_path_job *job, const mtsg_render_params *params, float *rgba
     }
     const size_t CH = multi ? (size_t)job->multiChannels : 5;
     std::lock_guard<std::mutex> lock(job->renderLock);
+    // the running render, for cancel(): from here to the return
+    struct Active {
+        mtsh_path_job *j;
+        explicit Active(mtsh_path_job *job) : j(job) { set(true); }
+        ~Active() { set(false); }
+        void set(bool on) {
+            std::lock_guard<std::mutex> sl(j->stateLock);
+            j->active = on;
+            j->cancel.store(0);   // a cancel() while idle has no effect
+        }
+    } running(job);
     const int n = (int)job->handles.size();
     const int b = job->border;
     if (params->tile_w <= 0 || params->tile_h <= 0) { g_perr = "tile rectangle outside the film"; return MTSG_ERR_INVALID; }
@@ -243,7 +259,6 @@ int job_render(mtsh_path_job *job, const mtsg_render_params *params, float *rgba
     std::vector<int> rcs(n, MTSG_OK);
     std::vector<double> sec(n, 0.0);
     std::vector<std::string> errs(n);
-    job->cancel.store(0);   // a cancel() while idle has no effect
     auto t0 = std::chrono::steady_clock::now();
     std::vector<std::thread> threads;
     for (int g = 0; g < n; ++g)
@@ -335,6 +350,10 @@ int mtsh_path_job_shares(const mtsh_path_job *job, int32_t *tiles, double *secon
 
 void mtsh_path_job_cancel(mtsh_path_job *job) {
     if (!job) return;
+    // (held to the end: the render this cancel is for cannot return, and the
+    // next one cannot start, while its GPUs are being told)
+    std::lock_guard<std::mutex> sl(job->stateLock);
+    if (!job->active) return;
     job->cancel.store(1);
     // only renders still running are told (see mtsh_path_job::sent)
     for (size_t g = 0; g < job->handles.size(); ++g) {
