@@ -168,7 +168,13 @@ typedef struct mtsg_bsdf {
     int32_t pad_tex[3];
 } mtsg_bsdf;
 
-enum { MTSG_EMITTER_AREA = 1, MTSG_EMITTER_ENVMAP = 2 };
+enum {
+    MTSG_EMITTER_AREA = 1, MTSG_EMITTER_ENVMAP = 2,
+    MTSG_EMITTER_POINT = 3,        /* src/emitters/point.cpp       */
+    MTSG_EMITTER_SPOT = 4,         /* src/emitters/spot.cpp        */
+    MTSG_EMITTER_DIRECTIONAL = 5,  /* src/emitters/directional.cpp */
+    MTSG_EMITTER_CONSTANT = 6      /* src/emitters/constant.cpp    */
+};
 
 #define MTSG_ENVMAP_MAX_LEVELS 24
 #define MTSG_MIPMAP_MAX_LEVELS 24
@@ -236,6 +242,31 @@ typedef struct mtsg_emitter {
     float radiance[3];
     float inv_area;          /* m_invSurfaceArea of the shape                */
 } mtsg_emitter;
+/* point / spot / directional / constant: shape = -1, cdf_offset = 0,
+ * inv_area = 0, and `radiance` holds m_intensity (point, spot),
+ * m_normalIrradiance (directional) or m_radiance (constant).  What else their
+ * sampleDirect reads is in the emitter's mtsg_emitter_ext. */
+
+/* Extension record of an emitter without a shape; one per emitter (zero for
+ * area and envmap emitters), mtsg_scene_desc::emitter_ext.
+ *   point        position = toWorld(0) (point.cpp:129)
+ *   spot         position; to_local = the 3x3 part of toWorld^-1, row-major
+ *                (falloffCurve(trafo.inverse()(-d)), spot.cpp:191); the
+ *                constants of SpotEmitter::configure (spot.cpp:90-93) and
+ *                m_cutoffAngle, in radians
+ *   directional  direction = toWorld(Vector(0, 0, 1)); the sphere of the
+ *                kd-tree's box, radius x 1.1 (directional.cpp:88-93)
+ *   constant     the sphere of Scene::getAABB() as createShape sees it (the
+ *                kd-tree's box expanded by the sensor), radius x 1.5 and at
+ *                least Epsilon (constant.cpp:67-71) */
+typedef struct mtsg_emitter_ext {
+    float position[3];
+    float direction[3];
+    float to_local[9];
+    float cos_beam_width, cos_cutoff_angle, cutoff_angle, inv_transition_width;
+    float bsphere_center[3], bsphere_radius;
+    float pad;
+} mtsg_emitter_ext;
 
 enum { MTSG_FILTER_BOX = 0, MTSG_FILTER_GAUSSIAN = 1 };
 
@@ -388,6 +419,11 @@ typedef struct mtsg_scene_desc {
      * om_bits[((id * SIZE + x) * SIZE + y) * (SIZE / 32) + z / 32] bit z % 32 */
     const mtsg_om *om;
     const uint32_t *om_bits;
+    /* n_emitters extension records, NULL when no emitter needs one.  Appended
+     * after every field of ABI 8, and read only when an emitter's type is
+     * MTSG_EMITTER_POINT or above: a caller compiled against the shorter
+     * struct never names such a type, so the version number stays. */
+    const mtsg_emitter_ext *emitter_ext;
 } mtsg_scene_desc;
 
 /* ---- render ------------------------------------------------------------- */
@@ -658,6 +694,18 @@ enum {
     MTSG_OPT_CAMERA_DIFFS = 7
 };
 int  mtsg_set_option(mtsg_scene *scene, int32_t key, int64_t value);
+
+/* Read-only: the shading kernels a handle's renders select (for the
+ * independent sampler; the other samplers shade with the generic material
+ * kernels).  *material_set = the material classes compiled in (1 diffuse,
+ * 2 roughconductor GGX, 4 other roughconductor, 8 dielectric; 15 = every
+ * class, also after MTSG_OPT_SHADE_GENERIC), + 16 when the scene holds one of
+ * the other BSDF plugins; *emitter_set = MTSG_EMITTER_SET_*: the scene's
+ * emitter kinds.  A scene with a point, spot, directional or constant emitter
+ * runs the "all kinds" kernels (generic materials); every other scene runs
+ * the kernels it ran before those kinds existed. */
+enum { MTSG_EMITTER_SET_AREA = 0, MTSG_EMITTER_SET_ENVMAP = 1, MTSG_EMITTER_SET_ALL = 2 };
+int  mtsg_scene_kernel_sets(mtsg_scene *scene, int32_t *material_set, int32_t *emitter_set);
 
 /* TEST ONLY: the traversal's limits, to exercise the kd-restart guard
  * (tests/test_gpu_edge_rays.py; kernels.h kd_restart).  stack_cap > 0

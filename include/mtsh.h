@@ -144,8 +144,21 @@ int32_t mtsh_scene_add_texture(mtsh_builder *b, const char *plugin, const mtsh_p
  * twosided's one or two BSDF ids (twosided.cpp:52-80), else none. */
 int32_t mtsh_scene_add_bsdf(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n_props,
                             const int32_t *nested, int32_t n_nested);
-/* Emitter: `area` (area.cpp:67-78; attach it to one shape) or `envmap`
- * (envmap.cpp:105-185; the scene's environment) -> emitter id. */
+/* Emitter -> emitter id.  The six plugins and their properties (every one
+ * also takes `samplingWeight`, emitter.cpp):
+ *   area         radiance; attach it to one shape (area.cpp:67-78)
+ *   envmap       filename, scale, toWorld; the scene's environment
+ *                (envmap.cpp:105-185)
+ *   point        intensity, and position or toWorld (point.cpp:57-68)
+ *   spot         intensity, cutoffAngle (20), beamWidth (3/4 of the cutoff),
+ *                toWorld, texture as a constant spectrum only: a texture id
+ *                among the properties is an error (spot.cpp:73-94)
+ *   directional  irradiance, and direction or toWorld without scale
+ *                (directional.cpp:54-72)
+ *   constant     radiance; the scene's environment, so not beside an envmap
+ *                (constant.cpp:43-49)
+ * Only `area` may be attached to a shape; myPath2_OM scenes take `area` and
+ * `envmap` alone. */
 int32_t mtsh_scene_add_emitter(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n_props);
 /* Shape group (shapegroup.cpp) -> group id for the shape calls' `group`. */
 int32_t mtsh_scene_add_group(mtsh_builder *b, const char *id);

@@ -63,7 +63,7 @@ DEV uint32_t block_append1(BlockAppend &ba, uint32_t *gcnt, bool p) {
 // radiance (ao: the value of a miss) and alpha to P.L, its refN to P.aux, and
 // the fan to D.F.
 // MATS: the material classes compiled in, as k_shade's (kernels.h MAT_*).
-template <bool ENV, int SMP, bool EXT, int MATS = MATS_ALL>
+template <int ENV, int SMP, bool EXT, int MATS = MATS_ALL>
 __global__ void __launch_bounds__(BLOCK) k_direct_shade(DevScene S, DevIntegrator I, DevBatch B, DevPaths P, DevDirect D, int hasAlpha) {
     __shared__ BlockAppend ba;
     const uint32_t slot = blockIdx.x * BLOCK + threadIdx.x;
@@ -100,6 +100,8 @@ __global__ void __launch_bounds__(BLOCK) k_direct_shade(DevScene S, DevIntegrato
         if (!valid) {
             if (D.ao) {
                 L = mk3(1.f, 1.f, 1.f);   // ao.cpp:91-95
+            } else if (ENV == EM_ALL && !(S.has_env & 1)) {   // a constant environment, or none
+                if (constant_emitter(S) >= 0 && !I.hide_emitters) L = L + ld3(S.emitters[constant_emitter(S)].radiance);
             } else if (ENV && !I.hide_emitters) {   // Scene::evalEnvironment of the differential camera ray
                 if (!S.cam_diffs) camera_ray_differentials<SMP>(*S.camDev, I, x, y, sIdx, rxd, ryd);
                 L = L + env_eval(S.env, rd, true, rxd, ryd);
@@ -154,9 +156,11 @@ __global__ void __launch_bounds__(BLOCK) k_direct_shade(DevScene S, DevIntegrato
                 const mtsg_emitter &E = S.emitters[ei];
                 float3 dd, value;
                 float dist, pdf;
-                bool accepted;
+                bool accepted, delta = false;
                 if (ENV && E.type == MTSG_EMITTER_ENVMAP) {
                     accepted = env_sample_direct(S.env, its.p, sx, sy, dd, dist, value, pdf);
+                } else if (ENV == EM_ALL && E.type >= MTSG_EMITTER_POINT) {
+                    accepted = emitter_sample_ext(S, E, ei, its.p, refN, sx, sy, dd, dist, value, pdf, delta);
                 } else {
                     float3 ep, en;
                     emitter_sample_position(S, E, ei, sx, sy, ep, en);
@@ -176,7 +180,8 @@ __global__ void __launch_bounds__(BLOCK) k_direct_shade(DevScene S, DevIntegrato
                     float bpdf;
                     const float3 bval = bsdf_eval<EXT, MATS>(S.bsdfs, bsdf, alb, wi, wo, bpdf);
                     if (!isZero(bval) && (!I.strict_normals || dot(its.geoN, dd) * wo.z > 0)) {
-                        const float weight = mis(pdf * D.fracLum, bpdf * D.fracBSDF) * D.weightLum;   // direct.cpp:238
+                        // direct.cpp:235-239: the BSDF pdf enters only for emitters on a surface sampled in solid angle
+                        const float weight = mis(pdf * D.fracLum, (ENV == EM_ALL && delta) ? 0.0f : bpdf * D.fracBSDF) * D.weightLum;
                         c = value * bval * weight;
                         if (!isZero(c)) {
                             emit = true;
@@ -243,7 +248,7 @@ __global__ void __launch_bounds__(BLOCK) k_direct_shade(DevScene S, DevIntegrato
 // shadow rays' cells in index order, then the BSDF rays' emitter or
 // environment hits in index order (direct.cpp:276-305); ao: the mean of the
 // cells (ao.cpp:118-122).
-template <bool ENV>
+template <int ENV>
 __global__ void __launch_bounds__(BLOCK) k_direct_resolve(DevScene S, DevIntegrator I, DevBatch B, DevPaths P, DevDirect D) {
     const uint32_t slot = blockIdx.x * BLOCK + threadIdx.x;
     if (slot >= B.nslots || camera_meta(B, slot).x == 0u) return;
@@ -274,6 +279,15 @@ __global__ void __launch_bounds__(BLOCK) k_direct_resolve(DevScene S, DevIntegra
                 // the environment, if any (direct.cpp:285-294; no BSDF of this
                 // build has a null component, so hideEmitters hides nothing here)
                 if (!ENV) continue;
+                if (ENV == EM_ALL && !(S.has_env & 1)) {   // a constant environment, or none
+                    const int ce = constant_emitter(S);
+                    float pdfSA;
+                    if (ce < 0 || !constant_miss(S, (uint32_t)ce, ro, rd, refN, pdfSA)) continue;
+                    const float lp = delta ? 0.0f : pdfSA * S.emitters[ce].pdf_discrete;
+                    const float w = mis(bv.w * D.fracBSDF, lp * D.fracLum) * D.weightBSDF;
+                    L = L + ld3(S.emitters[ce].radiance) * xyz(bv) * w;
+                    continue;
+                }
                 const float3 v = env_rot(S.env.E->to_local, rd);
                 float ux, uy;
                 env_uv(v, ux, uy);
@@ -304,6 +318,9 @@ void shade_smp(const DirectLaunch &a) {
     const dim3 g((a.B->nslots + BLOCK - 1) / BLOCK), b(BLOCK);
     const bool ext = a.ext && !a.D->ao;   // ao reads no BSDF
 #define SHADE(ENV, EXT, MATS) hipLaunchKernelGGL((k_direct_shade<ENV, SMP, EXT, MATS>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D, a.hasAlpha)
+    // a point, spot, directional or constant emitter: the kernel that holds
+    // every emitter kind (as launch_shade_smp; ao samples no emitter)
+    if (a.emx && !a.D->ao) { SHADE(EM_ALL, true, MATS_ALL); return; }
     // the smallest compiled material set that holds the scene's, for the
     // independent sampler (as launch_shade_smp picks k_shade's, smp_kernels.hip)
     if constexpr (SMP == MTSG_SAMPLER_INDEPENDENT) {
@@ -344,7 +361,8 @@ void launch_direct_shade(const DirectLaunch &a) {
 
 void launch_direct_resolve(const DirectLaunch &a) {
     const dim3 g((a.B->nslots + BLOCK - 1) / BLOCK), b(BLOCK);
-    if (a.env) hipLaunchKernelGGL((k_direct_resolve<true>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D);
+    if (a.emx) hipLaunchKernelGGL((k_direct_resolve<EM_ALL>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D);
+    else if (a.env) hipLaunchKernelGGL((k_direct_resolve<true>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D);
     else hipLaunchKernelGGL((k_direct_resolve<false>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D);
 }
 

@@ -200,6 +200,7 @@ struct ShadeLaunch {
     uint32_t shadeMin;   // k_finish
     bool env, ext, inst;   // inst: two-level instancing (k_finish<.., INST>)
     int mats;              // the scene's material classes (MAT_*), or MATS_ALL
+    bool emx = false;      // the scene holds an emitter without a shape: the EM_ALL kernels (EXT, MATS_ALL)
 };
 template <int SMP> void launch_shade_smp(const ShadeLaunch &a);
 template <int SMP> void launch_finish_smp(const ShadeLaunch &a);
@@ -284,6 +285,7 @@ struct DirectLaunch {
     int hasAlpha;
     bool env, ext;   // as ShadeLaunch
     int mats;        // the scene's material classes (MAT_*), or MATS_ALL
+    bool emx = false;   // as ShadeLaunch
 };
 void launch_direct_shade(const DirectLaunch &a);     // after the camera rays' trace launch: the fan
 void launch_direct_resolve(const DirectLaunch &a);   // after the fan's trace launch: P.L
@@ -3038,6 +3040,118 @@ DEV void emitter_sample_position(const DevScene &S, const mtsg_emitter &em, uint
     }
 }
 
+// The emitter kinds a shading kernel holds (the ENV parameter of shade_path,
+// k_shade, k_finish, k_direct_shade, k_direct_resolve): area lights only, with
+// the environment map, or every kind.  Scenes with a point, spot, directional
+// or constant emitter run the EM_ALL instantiations (mtsg_scene::emitterSet);
+// the first two sets are the kernels every other scene runs.
+enum : int { EM_AREA = 0, EM_ENV = 1, EM_ALL = 2 };
+constexpr float kInvFourPi = 0.07957747154594766788f;   // constants.h:66
+
+// BSphere::rayIntersect + solveQuadratic (bsphere.h:88-95, util.cpp:447-485)
+DEV bool sphere_intersect(float3 center, float radius, float3 o, float3 d, float &nearT, float &farT) {
+    const float3 oc = o - center;
+    const float A = dot(d, d), B = 2 * dot(oc, d), C = dot(oc, oc) - radius * radius;
+    if (A == 0) {
+        if (B != 0) { nearT = farT = -C / B; return true; }
+        return false;
+    }
+    const float discrim = B * B - 4.0f * A * C;
+    if (discrim < 0) return false;
+    const float sq = sqrtf(discrim), temp = B < 0 ? -0.5f * (B - sq) : -0.5f * (B + sq);
+    nearT = temp / A;
+    farT = C / temp;
+    if (nearT > farT) { const float t = nearT; nearT = farT; farT = t; }
+    return true;
+}
+
+// Emitter::sampleDirect of the emitters without a shape (point.cpp:127-142,
+// spot.cpp:105-127,179-193, directional.cpp:159-180, constant.cpp:173-215),
+// in the reference's operation order.  Their records travel in the emitter's
+// four emitRect rows (mtsg_scene_create packs them from mtsg_emitter_ext):
+//   point        {position, -}
+//   spot         {position, cosBeamWidth} {row 2 of toWorld^-1, cosCutoffAngle}
+//                {cutoffAngle, invTransitionWidth, -, -}: an untextured
+//                falloffCurve reads only the local z of the direction
+//   directional  {direction, sphere radius} {sphere centre, -}
+//   constant     {sphere centre, radius}
+// Returns false when the sample contributes nothing.  delta: the sample is in
+// the discrete measure, so the BSDF pdf stays out of its MIS weight
+// (path.cpp:192-196, direct.cpp:235-239).  None of Shape::sampleDirect's
+// rejection tests applies here.
+DEV bool emitter_sample_ext(const DevScene &S, const mtsg_emitter &E, uint32_t ei, float3 ref, float3 refN, float sx, float sy,
+                            float3 &dd, float &dist, float3 &value, float &pdf, bool &delta) {
+    const float4 *er = S.emitRect + 4 * (size_t)ei;
+    const float4 r0 = er[0];
+    delta = true;
+    pdf = 1.0f;
+    if (E.type == MTSG_EMITTER_POINT || E.type == MTSG_EMITTER_SPOT) {
+        dd = xyz(r0) - ref;
+        dist = sqrtf(dot(dd, dd));
+        const float invDist = 1.0f / dist;
+        dd = dd * invDist;
+        value = ld3(E.radiance);
+        if (E.type == MTSG_EMITTER_SPOT) {
+            const float4 r1 = er[1], r2 = er[2];
+            const float3 nd = -dd;
+            const float cosTheta = r1.x * nd.x + r1.y * nd.y + r1.z * nd.z;
+            if (cosTheta <= r1.w) return false;
+            if (!(cosTheta >= r0.w)) value = value * ((r2.x - mt_acosf(cosTheta)) * r2.y);
+        }
+        value = value * (invDist * invDist);
+        return true;
+    }
+    if (E.type == MTSG_EMITTER_DIRECTIONAL) {
+        const float3 d = xyz(r0);
+        const float3 diskCenter = xyz(er[1]) - d * r0.w;
+        const float distance = dot(ref - diskCenter, d);
+        if (distance < 0) return false;
+        dd = -d;
+        dist = distance;
+        value = ld3(E.radiance);
+        return true;
+    }
+    // constant: the cosine hemisphere about Frame(refN), or the uniform sphere
+    delta = false;
+    const bool hasN = !isZero(refN);
+    if (hasN) {
+        const float3 l = cosine_hemisphere(sx, sy);
+        pdf = kInvPi * l.z;
+        Frame3 f;
+        f.n = refN;
+        coordinateSystem(refN, f.s, f.t);
+        dd = f.toWorld(l);
+    } else {
+        const float z = 1.0f - 2.0f * sy;
+        const float r = sqrtf(fmaxf(0.0f, 1.0f - z * z));
+        float sinPhi, cosPhi;
+        mt_sincosf((float)(2.0 * 3.14159265358979323846 * (double)sx), &sinPhi, &cosPhi);   // 2.0f * M_PI * sample.x
+        dd = mk3(r * cosPhi, r * sinPhi, z);
+        pdf = kInvFourPi;
+    }
+    float nearT, farT;
+    if (!sphere_intersect(xyz(r0), r0.w, ref, dd, nearT, farT) || !(nearT < 0 && farT > 0)) return false;
+    dist = farT;
+    if (hasN && dot(dd, refN) <= 0) return false;
+    value = ld3(E.radiance) / pdf;
+    return true;
+}
+
+// ConstantBackgroundEmitter hit by a BSDF-sampled ray that left the scene
+// (path.cpp:236-246,257-265; fillDirectSamplingRecord and pdfDirect,
+// constant.cpp:217-261): false when the sphere test fails (no contribution);
+// pdfSA is the solid-angle density of sampling d from a vertex with normal refN
+DEV bool constant_miss(const DevScene &S, uint32_t ei, float3 o, float3 d, float3 refN, float &pdfSA) {
+    const float4 r0 = S.emitRect[4 * (size_t)ei];
+    float nearT, farT;
+    if (!sphere_intersect(xyz(r0), r0.w, o, d, nearT, farT) || nearT > 0 || farT < 0) return false;
+    pdfSA = !isZero(refN) ? kInvPi * fmaxf(0.0f, dot(d, refN)) : kInvFourPi;
+    return true;
+}
+// index of the scene's constant emitter (EM_ALL kernels; DevScene::has_env
+// holds 1 for an environment map, or 2 * (index + 1) for a constant one)
+DEV int constant_emitter(const DevScene &S) { return (S.has_env >> 1) - 1; }
+
 // Block-aggregated queue append: one LDS atomic per wave, one global atomic
 // per workgroup and queue (a contended global word costs ~11 ns per atomic).
 struct BlockAppend {
@@ -3172,7 +3286,7 @@ DEV PathLoads load_path_rest(const DevScene &S, const DevPaths &P, uint32_t i, b
 #define MTSG_SHADE_PRELOAD 0   // measured r04: 1 (all) C3 -0.5%, C5 -3.5% (spills at the 128-VGPR cap); 2 (hit) C3 -0.4%
 #endif
 
-template <bool ENV, int SMP, bool EXT, class Out, int MATS = MATS_ALL>
+template <int ENV, int SMP, bool EXT, class Out, int MATS = MATS_ALL>
 DEV void shade_path(const DevScene &S, const DevIntegrator &I, const DevBatch &B, const DevPaths &P, bool first, uint32_t i,
                     const uint4 meta, const PathLoads &pl, int hasAlpha, Out &out, bool &cont, bool &shadow,
                     const ShadeTables &tb) {
@@ -3203,7 +3317,9 @@ DEV void shade_path(const DevScene &S, const DevIntegrator &I, const DevBatch &B
         if (hasAlpha) L4.w = valid ? 1.0f : 0.0f;
         if (!valid) {
             // Scene::evalEnvironment of the differential camera ray (path.cpp:136-143)
-            if (ENV && !I.hide_emitters) {
+            if (ENV == EM_ALL && !(S.has_env & 1)) {   // a constant environment, or none
+                if (constant_emitter(S) >= 0 && !I.hide_emitters) L += ld3(tb.emitters[constant_emitter(S)].radiance);
+            } else if (ENV && !I.hide_emitters) {
                 float3 rxd, ryd;
                 if (S.cam_diffs) {
                     rxd = T;
@@ -3226,7 +3342,17 @@ DEV void shade_path(const DevScene &S, const DevIntegrator &I, const DevBatch &B
         // tail of the previous iteration after scene->rayIntersect (path.cpp:226-286)
         if (!valid) {
             // environment hit by the BSDF sample (path.cpp:236-246, 257-265)
-            if (ENV && !(I.hide_emitters && !(flags & F_SCATTERED))) {
+            if (ENV == EM_ALL && !(S.has_env & 1)) {
+                const int ce = constant_emitter(S);
+                if (ce >= 0 && !(I.hide_emitters && !(flags & F_SCATTERED))) {
+                    const float4 ax = ldS(&P.aux[i]);
+                    float pdfSA;
+                    if (constant_miss(S, (uint32_t)ce, ro, rd, xyz(ax), pdfSA)) {
+                        const float lumPdf = (flags & F_DELTA) ? 0.0f : pdfSA * tb.emitters[ce].pdf_discrete;
+                        L += T * ld3(tb.emitters[ce].radiance) * mis(ax.w, lumPdf);
+                    }
+                }
+            } else if (ENV && !(I.hide_emitters && !(flags & F_SCATTERED))) {
                 // evalEnvironment and pdfDirect look the same local
                 // direction up (envmap.cpp:386-387, 606-607): its atan2f /
                 // acosf are evaluated once for both
@@ -3295,9 +3421,11 @@ DEV void shade_path(const DevScene &S, const DevIntegrator &I, const DevBatch &B
                 const mtsg_emitter &E = tb.emitters[ei];
                 float3 dd, value;
                 float dist, pdf;
-                bool accepted;
+                bool accepted, delta = false;
                 if (ENV && E.type == MTSG_EMITTER_ENVMAP) {
                     accepted = env_sample_direct(S.env, its.p, sx, sy, dd, dist, value, pdf);
+                } else if (ENV == EM_ALL && E.type >= MTSG_EMITTER_POINT) {
+                    accepted = emitter_sample_ext(S, E, ei, its.p, refN, sx, sy, dd, dist, value, pdf, delta);
                 } else {
                     float3 ep, en;
                     emitter_sample_position(S, E, ei, sx, sy, ep, en);
@@ -3317,7 +3445,8 @@ DEV void shade_path(const DevScene &S, const DevIntegrator &I, const DevBatch &B
                     float bpdf;
                     const float3 bval = bsdf_eval<EXT, MATS>(S.bsdfs, bsdf, alb, wi, wo, bpdf);
                     if (!isZero(bval) && (!I.strict_normals || dot(its.geoN, dd) * wo.z > 0)) {
-                        const float weight = mis(pdf, bpdf);
+                        // the BSDF pdf enters only for emitters on a surface sampled in solid angle
+                        const float weight = mis(pdf, (ENV == EM_ALL && delta) ? 0.0f : bpdf);
                         const float3 c = T * value * bval * weight;
                         if (!isZero(c)) {
                             shadow = true;
@@ -3714,7 +3843,7 @@ constexpr int SHADE_LDS_BSDFS = 4, SHADE_LDS_EMITTERS = 16;
 // +3.0 ms; C3, no environment: +1.2 ms shade, -1.2 ms trace), so the sort is
 // compiled into the kernels of scenes with an environment emitter (misses and
 // environment sampling are their expensive events) and several classes
-template <bool ENV, int MATS>
+template <int ENV, int MATS>
 constexpr bool shade_sorted() { return MTSG_SHADE_SORT && ENV && (MATS & (MATS - 1)) != 0; }
 constexpr int SHADE_CLASSES = 6;
 DEV uint32_t shade_class(const DevScene &S, const DevBatch &B, const DevPaths &P, uint32_t i, bool first, const ShadeTables &tb) {
@@ -3761,7 +3890,7 @@ DEV uint32_t shade_sort(uint32_t cls, uint32_t *cnt, uint16_t *perm) {
 // lookup of a primary miss, hideEmitters' camera case), 0 = later bounces only
 // (that code compiled out: C5's kernel then holds 96 VGPRs without spilling),
 // 2 = either (run-time)
-template <bool ENV, int SMP, bool EXT, int MATS = MATS_ALL, int FIRST = 2>
+template <int ENV, int SMP, bool EXT, int MATS = MATS_ALL, int FIRST = 2>
 __global__ void SHADE_ATTR(ENV, MATS) k_shade(DevScene S, DevIntegrator I, DevBatch B, DevPaths P, int bounce, int qin,
                                                  uint32_t nIdentity, int hasAlpha) {
     __shared__ BlockAppend ba;
@@ -3900,7 +4029,7 @@ inline bool finish_uses_mats(int smp, bool ext, bool inst, int mats) {
 // INST: the two-level traversal (and its exact tie retrace) is compiled only
 // into the instantiations for instanced scenes, so the flat kernel carries
 // neither its registers nor the retrace's scratch stack
-template <bool ENV, int SMP, bool EXT, bool INST, int MATS = MATS_ALL>
+template <int ENV, int SMP, bool EXT, bool INST, int MATS = MATS_ALL>
 __global__ void FINISH_ATTR(MATS) k_finish(DevScene S, DevIntegrator I, DevBatch B, DevPaths P, int qin, int hasAlpha, uint32_t shadeMin) {
     const SpecStack stk{};
     lds_top_init(S);

@@ -144,6 +144,10 @@ struct mtsg_scene {
     bool extBsdfs = false;   // conductor / plastic / twosided records or textures present (k_shade<..., true>)
     int mats = MATS_ALL;     // material classes of the scene's records (k_shade<..., MATS>)
     bool shadeGeneric = false;   // MTSG_OPT_SHADE_GENERIC: the all-materials kernel (A/B tests)
+    // the scene's emitter kinds next to its material classes: EM_ALL with a
+    // point / spot / directional / constant emitter (the kernels that hold
+    // every kind), else EM_ENV / EM_AREA (the kernels those scenes always ran)
+    int emitterSet = EM_AREA;
     uint32_t nTextures = 0;
     const uint32_t *sobolM = nullptr;        // sobol sampler tables (device)
     const uint64_t *sobolVdc = nullptr, *sobolVdcInv = nullptr;
@@ -339,10 +343,11 @@ ShadeLaunch shade_args(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B,
     a.nIdentity = B.nslots;
     a.hasAlpha = s->cam.has_alpha || s->aovOn;   // multichannel: alpha is always a channel of the block
     a.shadeMin = s->finishShadeMin;
-    a.env = s->ds.has_env != 0;
+    a.env = (s->ds.has_env & 1) != 0;
     a.ext = s->extBsdfs;
     a.inst = s->ds.inst != nullptr;
-    a.mats = s->shadeGeneric ? (int)MATS_ALL : s->mats;
+    a.emx = s->emitterSet == EM_ALL;
+    a.mats = (s->shadeGeneric || a.emx) ? (int)MATS_ALL : s->mats;
     return a;
 }
 // where bounce 0 finds the camera rays' differentials (mtsg_scene::storeCamDiffs)
@@ -362,7 +367,8 @@ void launch_shade(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B, cons
     }
 }
 void launch_finish(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B, const DevPaths &P, int qin, hipStream_t st) {
-    const bool mats = finish_uses_mats(I.smp.type, s->extBsdfs, s->ds.inst != nullptr, s->shadeGeneric ? (int)MATS_ALL : s->mats);
+    const bool mats = finish_uses_mats(I.smp.type, s->extBsdfs, s->ds.inst != nullptr,
+                                       (s->shadeGeneric || s->emitterSet == EM_ALL) ? (int)MATS_ALL : s->mats);
     const ShadeLaunch a = shade_args(s, I, B, P, 1, qin, st, dim3(mats ? s->finishGridMats : s->finishGrid), dim3(TRACE_BLOCK));
     switch (I.smp.type) {
         case MTSG_SAMPLER_HALTON: launch_finish_smp<MTSG_SAMPLER_HALTON>(a); break;
@@ -619,8 +625,8 @@ struct RenderRun {
                         s->tileKeys.empty() ? nullptr : s->tileKeysDev};
     }
     DirectLaunch direct_args(uint32_t l) const {
-        return DirectLaunch{s->lstream[l], &s->ds, &I, &lane[l].B, &s->LP[l], &s->fan, s->cam.has_alpha, s->ds.has_env != 0, s->extBsdfs,
-                            s->shadeGeneric ? (int)MATS_ALL : s->mats};
+        return DirectLaunch{s->lstream[l], &s->ds, &I, &lane[l].B, &s->LP[l], &s->fan, s->cam.has_alpha, (s->ds.has_env & 1) != 0, s->extBsdfs,
+                            s->shadeGeneric ? (int)MATS_ALL : s->mats, s->emitterSet == EM_ALL};
     }
     FieldsLaunch fields(uint32_t l) const {
         return FieldsLaunch{s->lstream[l], &s->ds, &s->cam, &I, &lane[l].B, &s->LP[l], &s->aov, film, blockW, blockH, win};
@@ -1343,6 +1349,7 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
         return fail(rc);
     ds.blocks = dblocks; ds.root2 = root2;
     ds.triL = dtriL; ds.vpos = dvpos; ds.vnrm = dvnrm;
+    int constantEmitter = -1;   // index of the scene's constant environment emitter
     {
         // to_object rows of every rectangle, 48 B each (DevScene::rectM)
         std::vector<float4> rm((size_t)3 * std::max<uint32_t>(d->n_rects, 1u), make_float4(0, 0, 0, 0));
@@ -1367,9 +1374,56 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
             rs[2 * i + 1] = make_float4(R.dpdu[0], R.dpdu[1], R.dpdu[2], bef);
         }
         std::vector<float4> er((size_t)4 * std::max<uint32_t>(d->n_emitters, 1u), make_float4(0, 0, 0, 0));
+        int nEnvironment = 0;
         for (uint32_t e = 0; e < d->n_emitters; ++e) {
-            const int32_t sidx = d->emitters[e].shape;
+            const mtsg_emitter &em = d->emitters[e];
+            const int32_t sidx = em.shape;
             uint32_t type = (uint32_t)MTSG_SHAPE_MESH + 100u;   // not a shape emitter (environment)
+            // every kind is checked here: an unknown type must not fall
+            // through into the area sampling
+            if (em.type == MTSG_EMITTER_AREA) {
+            } else if (em.type == MTSG_EMITTER_ENVMAP) {
+                ++nEnvironment;
+                if (!d->has_envmap || d->envmap.emitter != (int32_t)e) {
+                    g_err = "emitter " + std::to_string(e) + ": envmap emitter without the scene's environment record";
+                    return fail(MTSG_ERR_INVALID);
+                }
+            } else if (em.type >= MTSG_EMITTER_POINT && em.type <= MTSG_EMITTER_CONSTANT) {
+                if (!d->emitter_ext) {
+                    g_err = "emitter " + std::to_string(e) + ": point / spot / directional / constant emitter without emitter_ext";
+                    return fail(MTSG_ERR_INVALID);
+                }
+                if (d->om) { g_err = "myPath2_OM scenes take area and envmap emitters only"; return fail(MTSG_ERR_INVALID); }
+                const mtsg_emitter_ext &x = d->emitter_ext[e];
+                s->emitterSet = EM_ALL;
+                // the rows emitter_sample_ext reads (kernels.h)
+                if (em.type == MTSG_EMITTER_POINT) {
+                    er[4 * e] = make_float4(x.position[0], x.position[1], x.position[2], 0.f);
+                } else if (em.type == MTSG_EMITTER_SPOT) {
+                    if (!(x.cos_cutoff_angle <= x.cos_beam_width) || !std::isfinite(x.inv_transition_width)) {
+                        g_err = "emitter " + std::to_string(e) + ": spot with inconsistent beam constants";
+                        return fail(MTSG_ERR_INVALID);
+                    }
+                    er[4 * e] = make_float4(x.position[0], x.position[1], x.position[2], x.cos_beam_width);
+                    er[4 * e + 1] = make_float4(x.to_local[6], x.to_local[7], x.to_local[8], x.cos_cutoff_angle);
+                    er[4 * e + 2] = make_float4(x.cutoff_angle, x.inv_transition_width, 0.f, 0.f);
+                } else if (em.type == MTSG_EMITTER_DIRECTIONAL) {
+                    er[4 * e] = make_float4(x.direction[0], x.direction[1], x.direction[2], x.bsphere_radius);
+                    er[4 * e + 1] = make_float4(x.bsphere_center[0], x.bsphere_center[1], x.bsphere_center[2], 0.f);
+                } else {
+                    ++nEnvironment;
+                    if (!(x.bsphere_radius > 0)) {
+                        g_err = "emitter " + std::to_string(e) + ": constant emitter without a bounding sphere";
+                        return fail(MTSG_ERR_INVALID);
+                    }
+                    er[4 * e] = make_float4(x.bsphere_center[0], x.bsphere_center[1], x.bsphere_center[2], x.bsphere_radius);
+                    constantEmitter = (int)e;
+                }
+            } else {
+                g_err = "emitter " + std::to_string(e) + ": unknown emitter type " + std::to_string(em.type);
+                return fail(MTSG_ERR_INVALID);
+            }
+            if (nEnvironment > 1) { g_err = "only one environment emitter (envmap or constant) is supported"; return fail(MTSG_ERR_INVALID); }
             if (sidx >= 0 && (uint32_t)sidx < d->n_shapes) {
                 const mtsg_shape &sh = d->shapes[sidx];
                 type = (uint32_t)sh.type;
@@ -1431,7 +1485,9 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
     // then collide, which only hides a tie of two such primitives)
     ds.instKeyStride = (uint64_t)d->n_prims * ((uint64_t)d->n_instances + 1) <= 0xFFFFFFFFull ? d->n_prims : 0x9E3779B1u;
     // environment emitter tables (envmap.h)
-    ds.has_env = d->has_envmap ? 1 : 0;
+    // (a constant environment: 2 * (index + 1), read by the EM_ALL kernels alone)
+    ds.has_env = d->has_envmap ? 1 : constantEmitter >= 0 ? 2 * (constantEmitter + 1) : 0;
+    if (s->emitterSet != EM_ALL) s->emitterSet = d->has_envmap ? EM_ENV : EM_AREA;
     s->mats = 0;
     for (uint32_t i = 0; i < d->n_bsdfs; ++i) {
         const mtsg_bsdf &b = d->bsdfs[i];
@@ -1684,6 +1740,15 @@ int mtsg_set_test_knobs(mtsg_scene *s, const mtsg_test_knobs *k) {
 int mtsg_set_finish_paths(mtsg_scene *s, uint32_t paths) {
     if (!s) return MTSG_ERR_INVALID;
     s->finishPaths = paths;
+    return MTSG_OK;
+}
+
+int mtsg_scene_kernel_sets(mtsg_scene *s, int32_t *material_set, int32_t *emitter_set) {
+    if (!s || !material_set || !emitter_set) { g_err = "null argument"; return MTSG_ERR_INVALID; }
+    // what shade_args hands the independent sampler's launchers
+    const bool emx = s->emitterSet == EM_ALL;
+    *material_set = mats_kernel_set((s->shadeGeneric || emx) ? (int)MATS_ALL : s->mats) + ((s->extBsdfs || emx) ? 16 : 0);
+    *emitter_set = emx ? MTSG_EMITTER_SET_ALL : (s->ds.has_env & 1) ? MTSG_EMITTER_SET_ENVMAP : MTSG_EMITTER_SET_AREA;
     return MTSG_OK;
 }
 
@@ -2043,7 +2108,7 @@ static int trace_rays(mtsg_scene *s, uint32_t n, const float *rays, float *t, fl
 
 int mtsg_env_eval(mtsg_scene *s, uint32_t n, const float *dirs, const float *rx, const float *ry, float *out) {
     if (!s || (!dirs && n) || (!out && n) || ((rx == nullptr) != (ry == nullptr))) { g_err = "invalid arguments"; return MTSG_ERR_INVALID; }
-    if (!s->ds.has_env) { g_err = "scene has no environment emitter"; return MTSG_ERR_INVALID; }
+    if (!(s->ds.has_env & 1)) { g_err = "scene has no environment emitter"; return MTSG_ERR_INVALID; }
     if (n == 0) return MTSG_OK;
     int rc;
     if ((rc = set_device(s)) != MTSG_OK) return rc;

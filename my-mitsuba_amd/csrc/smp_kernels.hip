@@ -37,8 +37,14 @@ void launch_shade_smp<MTSG_TU_SAMPLER>(const ShadeLaunch &a) {
         return;
     }
 #endif
+    // a scene with a point, spot, directional or constant emitter: the one
+    // kernel that holds every emitter kind (and every BSDF: EXT, MATS_ALL)
+    if (a.emx) {
+        hipLaunchKernelGGL((k_shade<EM_ALL, SMP, true>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
+        return;
+    }
     if (a.ext) {
-        if (a.env) hipLaunchKernelGGL((k_shade<true, SMP, true>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
+        if (a.env) hipLaunchKernelGGL((k_shade<true, SMP, true>),a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
         else hipLaunchKernelGGL((k_shade<false, SMP, true>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
         return;
     }
@@ -66,6 +72,10 @@ void launch_finish_mats(const ShadeLaunch &a) {
 }
 template <int SMP, bool INST>
 void launch_finish_inst(const ShadeLaunch &a) {
+    if (a.emx) {   // as launch_shade_smp
+        hipLaunchKernelGGL((k_finish<EM_ALL, SMP, true, INST>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.qin, a.hasAlpha, a.shadeMin);
+        return;
+    }
     if (a.ext) {
         if (a.env) hipLaunchKernelGGL((k_finish<true, SMP, true, INST>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.qin, a.hasAlpha, a.shadeMin);
         else hipLaunchKernelGGL((k_finish<false, SMP, true, INST>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.qin, a.hasAlpha, a.shadeMin);

@@ -295,7 +295,12 @@ void Scene::finalize() {
         ed.type = e.type;
         ed.shape = e.shape;
         for (int k = 0; k < 3; ++k) ed.radiance[k] = e.radiance[k];
-        if (e.type == MTSG_EMITTER_ENVMAP) {   // tables are built after the kd-tree (needs its AABB)
+        if (e.type >= MTSG_EMITTER_POINT && integrator.type == "myPath2_OM")
+            throw std::runtime_error("myPath2_OM: point, spot, directional and constant emitters are outside this build's scope "
+                                     "(their occupancy-map visibility is not implemented)");
+        // envmap: tables are built after the kd-tree (needs its AABB), as are
+        // the extension records of the emitters without a shape
+        if (e.type != MTSG_EMITTER_AREA) {
             emitterDesc.push_back(ed);
             wsum += e.samplingWeight;
             emitterCdf.push_back(wsum);
@@ -576,6 +581,53 @@ void Scene::finalize() {
         d.env_cdf_rows = envCdfRows.data();
         d.env_cdf_cols = envCdfCols.data();
         d.env_row_weights = envRowWeights.data();
+    }
+    // ---------------- point / spot / directional / constant ----------------
+    // one extension record per emitter, in the order of `emitters`; created
+    // where Scene::initializeBidirectional calls Emitter::createShape
+    // (scene.cpp:410-440): Scene::getAABB() is then the tree's box expanded
+    // by the sensor alone, for every emitter
+    emitterExt.clear();
+    d.emitter_ext = nullptr;
+    bool anyExt = false;
+    for (auto &e : emitters) anyExt |= e.type >= MTSG_EMITTER_POINT;
+    if (anyExt) {
+        emitterExt.assign(emitters.size(), mtsg_emitter_ext{});
+        const float camPos[3] = {cam.camera_to_world[3], cam.camera_to_world[7], cam.camera_to_world[11]};
+        for (size_t i = 0; i < emitters.size(); ++i) {
+            const Emitter &e = emitters[i];
+            mtsg_emitter_ext &x = emitterExt[i];
+            if (e.type == MTSG_EMITTER_POINT || e.type == MTSG_EMITTER_SPOT) {
+                // trafo.transformAffine(Point(0.0f)) (point.cpp:129, spot.cpp:181)
+                const V3 p = e.toWorld.pointAffine(V3(0.0f));
+                for (int k = 0; k < 3; ++k) x.position[k] = p[k];
+            }
+            if (e.type == MTSG_EMITTER_SPOT) {
+                for (int r = 0; r < 3; ++r)
+                    for (int c = 0; c < 3; ++c) x.to_local[3 * r + c] = e.toWorld.inv[r][c];
+                // SpotEmitter::configure (spot.cpp:90-93)
+                x.cos_beam_width = std::cos(e.beamWidth);
+                x.cos_cutoff_angle = std::cos(e.cutoffAngle);
+                x.cutoff_angle = e.cutoffAngle;
+                x.inv_transition_width = 1.0f / (e.cutoffAngle - e.beamWidth);
+            } else if (e.type == MTSG_EMITTER_DIRECTIONAL) {
+                // trafo(Vector(0,0,1)) (directional.cpp:161); the kd-tree
+                // box's sphere x 1.1 (directional.cpp:88-93)
+                const V3 dir = e.toWorld.vector(V3(0, 0, 1));
+                V3 c;
+                for (int k = 0; k < 3; ++k) { x.direction[k] = dir[k]; c[k] = (d.aabb_min[k] + d.aabb_max[k]) * 0.5f; }
+                const V3 mx(d.aabb_max[0], d.aabb_max[1], d.aabb_max[2]);
+                for (int k = 0; k < 3; ++k) x.bsphere_center[k] = c[k];
+                x.bsphere_radius = length(c - mx);
+                x.bsphere_radius *= 1.1f;
+            } else if (e.type == MTSG_EMITTER_CONSTANT) {
+                // scene->getAABB().getBSphere() x 1.5, at least Epsilon (constant.cpp:67-71)
+                float radius;
+                sceneBoundingSphere(d.aabb_min, d.aabb_max, camPos, x.bsphere_center, radius);
+                x.bsphere_radius = std::max(1e-4f, radius * 1.5f);
+            }
+        }
+        d.emitter_ext = emitterExt.data();
     }
 }
 

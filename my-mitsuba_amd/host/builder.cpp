@@ -506,8 +506,79 @@ int SceneBuilder::defaultBsdf(bool emitter) {
     return (int)scene.bsdfs.size() - 1;
 }
 
-int SceneBuilder::emitter(const std::string &type_, const Properties &props, int line) {
+// Transform::hasScale (transform.h:76-90)
+static bool hasScale(const Transform &t) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) {
+            float sum = 0;
+            for (int k = 0; k < 3; ++k) sum += t.m[i][k] * t.m[j][k];
+            if (i == j && std::abs(sum - 1) > 1e-3f) return true;
+            if (i != j && std::abs(sum) > 1e-3f) return true;
+        }
+    return false;
+}
+
+// degToRad (util.h:297): the float times the double M_PI / 180.0f
+static float degToRad(float v) { return (float)((double)v * (M_PI / (double)180.0f)); }
+
+int SceneBuilder::emitter(const std::string &type_, const Properties &props, int line, bool nestedTexture) {
     const std::string type = lower(type_);
+    if (nestedTexture && type != "spot") throw err(at(line) + "emitter \"" + type + "\" takes no texture");
+    if (type == "point" || type == "spot" || type == "directional" || type == "constant") {
+        Emitter e;
+        e.samplingWeight = props.getFloat("samplingWeight", 1.0f);
+        if (type == "point") {
+            // PointEmitter(props) (point.cpp:57-68)
+            e.type = MTSG_EMITTER_POINT;
+            e.toWorld = props.getTransform("toWorld", Transform());
+            if (props.points.count("position")) {
+                if (props.transforms.count("toWorld")) throw err("Only one of the parameters 'position' and 'toWorld' can be used!'");
+                e.toWorld = Transform::translate(props.points.at("position"));
+            }
+            e.radiance = props.getSpectrum("intensity", V3(1.0f));   // D65 == 1 in RGB mode
+        } else if (type == "spot") {
+            // SpotEmitter(props) (spot.cpp:73-83)
+            if (nestedTexture)
+                throw err(at(line) + "spot: a nested <texture> is outside this build's scope (its 'texture' is accepted as a constant spectrum only)");
+            e.type = MTSG_EMITTER_SPOT;
+            e.toWorld = props.getTransform("toWorld", Transform());
+            e.radiance = props.getSpectrum("intensity", V3(1.0f));
+            const float cutoff = props.getFloat("cutoffAngle", 20);
+            const float beam = props.getFloat("beamWidth", cutoff * 3.0f / 4.0f);
+            e.beamWidth = degToRad(beam);
+            e.cutoffAngle = degToRad(cutoff);
+            if (!(e.cutoffAngle >= e.beamWidth)) throw err(at(line) + "spot: Assert(m_cutoffAngle >= m_beamWidth) failed");
+            // a ConstantSpectrumTexture never enters falloffCurve (spot.cpp:112-119)
+            props.getSpectrum("texture", V3(1.0f));
+        } else if (type == "directional") {
+            // DirectionalEmitter(props) (directional.cpp:54-72)
+            e.type = MTSG_EMITTER_DIRECTIONAL;
+            e.radiance = props.getSpectrum("irradiance", V3(1.0f));
+            if (props.points.count("direction")) {
+                if (props.transforms.count("toWorld")) throw err("Only one of the parameters 'direction' and 'toWorld'can be used at a time!");
+                const V3 d = normalize(props.points.at("direction"));
+                V3 u, unused;
+                coordinateSystem(d, u, unused);
+                try {
+                    e.toWorld = Transform::lookAt(V3(0.0f), d, u);
+                } catch (const std::exception &ex) {
+                    throw err(at(line) + "directional: " + ex.what());
+                }
+            } else {
+                e.toWorld = props.getTransform("toWorld", Transform());
+                if (hasScale(e.toWorld)) throw err("Scale factors in the emitter-to-world transformation are not allowed!");
+            }
+        } else {
+            // ConstantBackgroundEmitter(props) (constant.cpp:43-49)
+            for (auto &o : scene.emitters)
+                if (o.type == MTSG_EMITTER_ENVMAP || o.type == MTSG_EMITTER_CONSTANT)
+                    throw err("only one environment emitter is supported (Scene::m_environmentEmitter)");
+            e.type = MTSG_EMITTER_CONSTANT;
+            e.radiance = props.getSpectrum("radiance", V3(1.0f));
+        }
+        scene.emitters.push_back(e);
+        return (int)scene.emitters.size() - 1;
+    }
     if (type == "area") {
         // AreaLight(props) (area.cpp:67-78): attached to the shape that names it
         if (props.transforms.count("toWorld"))
@@ -519,10 +590,12 @@ int SceneBuilder::emitter(const std::string &type_, const Properties &props, int
         return (int)scene.emitters.size() - 1;
     }
     if (type != "envmap")
-        throw err(at(line) + "emitter plugin \"" + type + "\" is outside this build's scope (only 'area' and 'envmap')");
+        throw err(at(line) + "emitter plugin \"" + type + "\" is outside this build's scope (only 'area', 'envmap', 'point', 'spot', "
+                  "'directional' and 'constant')");
     // EnvironmentMap(props) (envmap.cpp:105-185)
     for (auto &e : scene.emitters)
-        if (e.type == MTSG_EMITTER_ENVMAP) throw err("only one environment emitter is supported (Scene::m_environmentEmitter)");
+        if (e.type == MTSG_EMITTER_ENVMAP || e.type == MTSG_EMITTER_CONSTANT)
+            throw err("only one environment emitter is supported (Scene::m_environmentEmitter)");
     Emitter e;
     e.type = MTSG_EMITTER_ENVMAP;
     e.samplingWeight = props.getFloat("samplingWeight", 1.0f);
@@ -1070,7 +1143,17 @@ void Scene::buildDirect() {
         if (len < 0) {
             const float camPos[3] = {camera.camera_to_world[3], camera.camera_to_world[7], camera.camera_to_world[11]};
             float center[3], radius;
-            sceneBoundingSphere(desc.aabb_min, desc.aabb_max, camPos, center, radius);
+            // scene->getBSphere() after Scene::initialize: the box holds the
+            // emitters' getAABB() too (scene.cpp:424-439): the position of a
+            // point or spot light, the sphere centre of a constant one
+            std::vector<float> pts;
+            for (size_t i = 0; i < emitterExt.size(); ++i) {
+                const int t = emitterDesc[i].type;
+                const float *p = t == MTSG_EMITTER_POINT || t == MTSG_EMITTER_SPOT ? emitterExt[i].position
+                                 : t == MTSG_EMITTER_CONSTANT ? emitterExt[i].bsphere_center : nullptr;
+                if (p) pts.insert(pts.end(), p, p + 3);
+            }
+            sceneBoundingSphere(desc.aabb_min, desc.aabb_max, camPos, pts.data(), pts.size() / 3, center, radius);
             len = radius * 0.5f;
         }
         directDesc.ao_ray_length = len;

@@ -160,7 +160,11 @@ int32_t mtsh_scene_add_bsdf(mtsh_builder *b, const char *plugin, const mtsh_prop
 }
 
 int32_t mtsh_scene_add_emitter(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n) {
-    return guarded(b, [&] { return (int32_t)b->b->emitter(plugin ? plugin : "", toProps(props, n)); });
+    return guarded(b, [&] {
+        std::map<std::string, int> tex;   // a texture id among the properties: spot's nested texture
+        mtsh::Properties pr = toProps(props, n, &tex);
+        return (int32_t)b->b->emitter(plugin ? plugin : "", pr, 0, !tex.empty());
+    });
 }
 
 int32_t mtsh_scene_add_group(mtsh_builder *b, const char *id) {

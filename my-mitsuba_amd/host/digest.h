@@ -41,6 +41,7 @@ inline std::vector<mtsh_digest_entry> sceneDigest(const mtsg_scene_desc &d) {
     s.instances = nullptr; s.groups = nullptr; s.textures = nullptr;
     s.tex_texels = s.tri_uv = s.tri_dpdv = nullptr;
     s.om = nullptr; s.om_bits = nullptr;
+    s.emitter_ext = nullptr;
     add("scalars", &s, sizeof(s));
     add("vtx_pos", d.vtx_pos, sizeof(float) * 3 * (size_t)d.n_vertices);
     add("vtx_nrm", d.vtx_nrm, sizeof(float) * 3 * (size_t)d.n_vertices);
@@ -84,6 +85,7 @@ inline std::vector<mtsh_digest_entry> sceneDigest(const mtsg_scene_desc &d) {
         add("om", d.om, sizeof(mtsg_om));
         add("om_bits", d.om_bits, sizeof(uint32_t) * MTSG_OM_COUNT * MTSG_OM_SIZE * MTSG_OM_SIZE * (MTSG_OM_SIZE / 32));
     }
+    if (d.emitter_ext) add("emitter_ext", d.emitter_ext, sizeof(mtsg_emitter_ext) * (size_t)d.n_emitters);
     return out;
 }
 

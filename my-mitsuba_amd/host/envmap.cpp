@@ -32,7 +32,22 @@ void sceneBoundingSphere(const float aabbMin[3], const float aabbMax[3], const f
     radius = std::sqrt(dx * dx + dy * dy + dz * dz);
 }
 
-void buildEnvmap(const Emitter &e, const float aabbMin[3], const float aabbMax[3], const float camPos[3],
+void sceneBoundingSphere(const float aabbMin[3], const float aabbMax[3], const float camPos[3], const float *emitterPts, size_t n,
+                         float center[3], float &radius) {
+    float mn[3], mx[3];
+    for (int k = 0; k < 3; ++k) {
+        mn[k] = std::min(aabbMin[k], camPos[k]);
+        mx[k] = std::max(aabbMax[k], camPos[k]);
+        for (size_t i = 0; i < n; ++i) {
+            mn[k] = std::min(mn[k], emitterPts[3 * i + k]);
+            mx[k] = std::max(mx[k], emitterPts[3 * i + k]);
+        }
+    }
+    const float zero[3] = {mn[0], mn[1], mn[2]};   // already inside: the sensor term changes nothing
+    sceneBoundingSphere(mn, mx, zero, center, radius);
+}
+
+void buildEnvmap(const Emitter &e,const float aabbMin[3], const float aabbMax[3], const float camPos[3],
                  std::vector<float> &texels, std::vector<float> &cdfRows, std::vector<float> &cdfCols,
                  std::vector<float> &rowWeights, mtsg_envmap &env) {
     memset(&env, 0, sizeof(env));

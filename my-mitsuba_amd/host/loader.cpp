@@ -777,7 +777,11 @@ struct Loader {
         Properties props;
         std::vector<XNode *> nested;
         parseProps(n, props, nested);
-        return B.emitter(n.attr("type"), props, n.line);
+        // a texture object among the children (SpotEmitter::addChild, spot.cpp:206-212)
+        bool nestedTexture = false;
+        for (XNode *c : nested)
+            if (c->tag == "texture" || (c->tag == "ref" && textureIds.count(c->attr("id")))) nestedTexture = true;
+        return B.emitter(n.attr("type"), props, n.line, nestedTexture);
     }
 
     void parseShape(XNode &n, int group) {

@@ -73,7 +73,9 @@ struct Emitter {
     int width = 0, height = 0;       // level-0 size
     std::vector<float> rgb;          // level 0, RGB float, top row first (after the PFM flip)
     float scale = 1.0f;
-    Transform toWorld;
+    Transform toWorld;               // envmap; point / spot / directional: m_worldTransform
+    // spot (src/emitters/spot.cpp:73-94), radians
+    float cutoffAngle = 0, beamWidth = 0;
 };
 
 // `bitmap` texture (src/textures/bitmap.cpp): its pyramid lives in
@@ -201,6 +203,7 @@ struct Scene {
     std::vector<mtsg_shape> shapeDesc;
     std::vector<mtsg_bsdf> bsdfDesc;
     std::vector<mtsg_emitter> emitterDesc;
+    std::vector<mtsg_emitter_ext> emitterExt;   // one per emitter; empty unless a point / spot / directional / constant emitter exists
     std::vector<mtsg_triaccel> triaccel;
     std::vector<float> envTexels, envCdfRows, envCdfCols, envRowWeights;
     std::vector<uint32_t> qmcPrimes, qmcOffsets;
@@ -238,6 +241,10 @@ extern int g_instancing;         // MTSH_INSTANCING_* of the next load
 // kd-tree AABB expanded by the sensor position, and the sphere around its
 // centre through its maximum corner
 void sceneBoundingSphere(const float aabbMin[3], const float aabbMax[3], const float camPos[3], float center[3], float &radius);
+// ... and the same box expanded further by the emitters' getAABB() (n points of
+// 3 floats): Scene::getAABB() once initializeBidirectional has returned
+void sceneBoundingSphere(const float aabbMin[3], const float aabbMax[3], const float camPos[3], const float *emitterPts, size_t n,
+                         float center[3], float &radius);
 
 // Environment emitter tables (envmap.cpp in this directory)
 void buildEnvmap(const Emitter &e, const float aabbMin[3], const float aabbMax[3], const float camPos[3],
@@ -309,7 +316,9 @@ public:
     // textures: BSDF parameter name -> texture id; nested: twosided's BSDFs
     int bsdf(const std::string &type, const Properties &props, const std::map<std::string, int> &textures,
              const std::vector<int> &nested, const std::string &id, int line = 0);
-    int emitter(const std::string &type, const Properties &props, int line = 0);   // area (for a shape) or envmap
+    // area (for a shape), envmap, point, spot, directional or constant;
+    // nestedTexture: the emitter has a texture object among its children
+    int emitter(const std::string &type, const Properties &props, int line = 0, bool nestedTexture = false);
     // shapes: bsdf / emitter -1 = none; group -1 = the scene
     void shape(const std::string &type, const Properties &props, int bsdf, int emitter, int group, int line = 0);
     void mesh(Mesh &&m, const Transform *toWorld, bool flipNormals, int bsdf, int emitter, int group);

@@ -40,6 +40,9 @@ MTSG_INTEGRATOR_PATH = 0
 MTSG_INTEGRATOR_PATH2_OM = 1
 MTSG_INTEGRATOR_DIRECT = 2
 MTSG_INTEGRATOR_AO = 3
+# mtsg_emitter.type
+MTSG_EMITTER_AREA, MTSG_EMITTER_ENVMAP, MTSG_EMITTER_POINT, MTSG_EMITTER_SPOT = 1, 2, 3, 4
+MTSG_EMITTER_DIRECTIONAL, MTSG_EMITTER_CONSTANT = 5, 6
 
 
 class RenderParams(C.Structure):
@@ -308,7 +311,7 @@ DEVICE_SYMBOLS = [
     "mtsg_sampler_draws", "mtsg_debug_wavetimes", "mtsg_set_tile_callback",
     "mtsg_debug_stragglers", "mtsg_set_test_knobs", "mtsg_set_option",
     "mtsg_scene_set_aov", "mtsg_render_multi", "mtsg_render_device_multi", "mtsg_render_device_tiles_multi",
-    "mtsg_render_samples_multi", "mtsg_scene_set_direct",
+    "mtsg_render_samples_multi", "mtsg_scene_set_direct", "mtsg_scene_kernel_sets",
 ]
 HOST_SYMBOLS = [
     "mtsh_scene_load", "mtsh_scene_load_overrides", "mtsh_scene_load_props", "mtsh_scene_set_scene_props", "mtsh_set_kd_threads", "mtsh_set_instancing", "mtsh_scene_desc", "mtsh_scene_render_params",
@@ -470,6 +473,8 @@ def device_lib() -> C.CDLL:
         lib.mtsg_set_batch_paths.argtypes = [C.c_void_p, C.c_uint32]
         lib.mtsg_set_finish_paths.argtypes = [C.c_void_p, C.c_uint32]
         lib.mtsg_set_option.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
+        if hasattr(lib, "mtsg_scene_kernel_sets"):   # (an MTSG_LIB build from before the query; GPUScene.kernel_sets then raises)
+            lib.mtsg_scene_kernel_sets.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.mtsg_trace_closest.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mtsg_trace_shadow.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1040,6 +1045,13 @@ class GPUScene:
     def set_option(self, key: int, value: int) -> None:
         """An execution option (MTSG_OPT_*, mtsg_set_option): scheduling only, never pixels."""
         self._check(device_lib().mtsg_set_option(self._h, key, value), "mtsg_set_option")
+
+    def kernel_sets(self) -> tuple:
+        """(material set, emitter set) of the shading kernels the handle's renders select
+        (mtsg_scene_kernel_sets; emitter set: 0 area only, 1 with the envmap, 2 every kind)."""
+        m, e = C.c_int32(), C.c_int32()
+        self._check(device_lib().mtsg_scene_kernel_sets(self._h, C.byref(m), C.byref(e)), "mtsg_scene_kernel_sets")
+        return m.value, e.value
 
     def stats(self) -> Stats:
         s = Stats()
