@@ -270,8 +270,13 @@ typedef struct mtsg_emitter_ext {
 
 enum { MTSG_FILTER_BOX = 0, MTSG_FILTER_GAUSSIAN = 1 };
 
-/* Perspective sensor + film, precomputed host side
- * (src/sensors/perspective.cpp:126-176, src/librender/sensor.cpp:241-262). */
+enum { MTSG_SENSOR_PERSPECTIVE = 0, MTSG_SENSOR_THINLENS = 1 };
+
+/* Perspective or thinlens sensor + film, precomputed host side
+ * (src/sensors/perspective.cpp:126-176 = src/sensors/thinlens.cpp:156-212,
+ * src/librender/sensor.cpp:241-262).  The thinlens sensor draws an aperture
+ * sample after the pixel jitter (integrator.cpp:178-186, thinlens.cpp:324-361):
+ * every later dimension of a sample moves by two. */
 typedef struct mtsg_camera {
     float sample_to_camera[16];   /* row-major 4x4                          */
     float camera_to_world[12];    /* row-major 3x4 affine                   */
@@ -287,7 +292,9 @@ typedef struct mtsg_camera {
     int32_t border;               /* ceil(radius - 0.5)                     */
     float filter_values[32];      /* MTS_FILTER_RESOLUTION + 1 entries      */
     int32_t has_alpha;            /* film stores a real alpha channel       */
-    int32_t pad[3];
+    int32_t sensor_type;          /* MTSG_SENSOR_* (0: perspective)         */
+    float aperture_radius;        /* thinlens: m_apertureRadius > 0         */
+    float focus_distance;         /* thinlens: m_focusDistance > 0          */
 } mtsg_camera;
 
 /* Sampler.  The path's sample dimensions are drawn in the
@@ -805,6 +812,15 @@ void mtsg_kd_free(mtsg_kd_tree *tree);
  * dimensions reserved to the arrays, as in a render. */
 int  mtsg_sampler_draws(mtsg_scene *scene, const mtsg_render_params *params, int x, int y, uint32_t s,
                         uint32_t n, const int32_t *kinds, float *out);
+
+/* Debug: the camera rays k_camera produces for n samples of params' rectangle,
+ * xys = (x, y, s) triples in film coordinates.  Per sample 14 floats out:
+ * origin, direction, mint, maxt as bounce 0 reads them (a perspective flat
+ * scene: rebuilt from its 16-B record), then the x and y differential
+ * directions scaled by 1/sqrt(spp) (integrator.cpp:148-149; their origins are
+ * the ray's; zeros for myPath2_OM, which takes none).  perspective.cpp:271-298,
+ * thinlens.cpp:324-361.  The rectangle x spp may hold at most 2^22 slots. */
+int  mtsg_camera_rays(mtsg_scene *scene, const mtsg_render_params *params, uint32_t n, const int32_t *xys, float *out);
 
 int  mtsg_trace_closest(mtsg_scene *scene, uint32_t n, const float *rays,
                         float *t, float *u, float *v, uint32_t *prim);

@@ -171,7 +171,10 @@ int32_t mtsh_scene_add_shape(mtsh_builder *b, const char *plugin, const mtsh_pro
 int32_t mtsh_scene_add_mesh(mtsh_builder *b, const mtsh_mesh *mesh, int32_t bsdf, int32_t emitter, int32_t group);
 /* Instance of a shape group (instance.cpp:57-130); props: its `toWorld`. */
 int32_t mtsh_scene_add_instance(mtsh_builder *b, int32_t group, const mtsh_prop *props, int32_t n_props);
-/* The sensor and what it holds (sensor.cpp:150-262, hdrfilm.cpp:209-220,
+/* The sensor and what it holds (sensor.cpp:150-278, hdrfilm.cpp:209-220,
+ * `perspective` or `thinlens`, thinlens.cpp:122-143: a plugin passes the name and
+ * the Properties of Scene::getSensor() through; fov / fovAxis or focalLength,
+ * toWorld, nearClip, farClip, and for thinlens apertureRadius, focusDistance;
  * rfilter.cpp, independent.cpp / halton.cpp / ...), the integrator
  * (integrator.cpp:199-234; myPath2_OM.cpp:61-85).  Return 0 or -1. */
 int32_t mtsh_scene_set_sensor(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n_props);

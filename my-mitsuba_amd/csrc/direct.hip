@@ -86,7 +86,8 @@ __global__ void __launch_bounds__(BLOCK) k_direct_shade(DevScene S, DevIntegrato
         int x, y;
         uint32_t sIdx;
         slot_pixel(B, slot, x, y, sIdx);
-        smp = path_sampler(I, x, y, sIdx, 2u, 1u);   // after the camera's pixel jitter (camera_meta)
+        // after the camera's pixel jitter and a thinlens sensor's aperture sample (camera_meta)
+        smp = path_sampler(I, x, y, sIdx, 2u + 2u * B.sensorDraws, 1u + B.sensorDraws);
         const bool valid = __float_as_uint(h.w) != 0xFFFFFFFFu;
         float3 L = mk3(0, 0, 0);
         // RadianceQueryRecord::rayIntersect (records.inl:117-143)

@@ -113,6 +113,9 @@ struct DevCamera {
     int diffs;            // store primary-ray differentials (environment / filtered texture lookups)
     int compact;          // store ray_d = (direction, 1/z) only (DevScene::camCompact)
     int crop_w, crop_h;   // the sampler's space partition (setFilmResolution)
+    // thinlens (thinlens.cpp:122-143): k_camera_lens instead of k_camera
+    int lens;
+    float aperture_radius, focus_distance;
 };
 
 struct DevIntegrator {
@@ -133,6 +136,9 @@ struct DevBatch {
     uint32_t s0, ns;
     uint32_t nslots;
     const int32_t *keys;                  // mtsg_set_tile_list: deal key of virtual tile v = keys[v] (device); null: arithmetic
+    // 2D requests the sensor makes after the pixel jitter (0; thinlens: 1, its
+    // aperture sample, integrator.cpp:178-186): where bounce 0's draws start (camera_meta)
+    uint32_t sensorDraws;
 };
 // deal key of virtual tile v of a call
 __host__ __device__ inline int batch_key(const DevBatch &B, int v) { return B.keys ? B.keys[v] : B.toffset + v * B.tstride; }
@@ -2172,7 +2178,8 @@ DEV uint4 camera_meta(const DevBatch &B, uint32_t slot) {
     uint32_t s;
     slot_pixel(B, slot, x, y, s);
     const bool alive = x < B.rect_x + B.rect_w && y < B.rect_y + B.rect_h;
-    return alive ? make_uint4(1u, 2u, slot, 1u) : make_uint4(0u, 0u, slot, 0u);
+    // (a thinlens sensor: its aperture sample too, dimension 4 after two requests)
+    return alive ? make_uint4(1u, 2u + 2u * B.sensorDraws, slot, 1u + B.sensorDraws) : make_uint4(0u, 0u, slot, 0u);
 }
 
 __global__ void __launch_bounds__(BLOCK) k_camera(DevCamera C, DevIntegrator I, DevBatch B, DevPaths P) {
@@ -2221,6 +2228,93 @@ __global__ void __launch_bounds__(BLOCK) k_camera(DevCamera C, DevIntegrator I, 
             if (I.om) stS(&P.meta[slot], make_uint4(0u, 0u, slot, 0u));
             stS(&P.L[slot], make_float4(0.f, 0.f, 0.f, 0.f));
         }
+    }
+}
+
+// warp.cpp:81-102 squareToUniformDiskConcentric
+DEV void uniform_disk_concentric(float sx, float sy, float &px, float &py) {
+    float r1 = 2.0f * sx - 1.0f, r2 = 2.0f * sy - 1.0f;
+    float phi, r;
+    if (r1 == 0 && r2 == 0) { r = phi = 0; }
+    else if (r1 * r1 > r2 * r2) { r = r1; phi = (kPi / 4.0f) * (r2 / r1); }
+    else { r = r2; phi = (kPi / 2.0f) - (r1 / r2) * (kPi / 4.0f); }
+    float sinPhi, cosPhi;
+    mt_sincosf(phi, &sinPhi, &cosPhi);
+    px = r * cosPhi;
+    py = r * sinPhi;
+}
+DEV float3 camera_to_world_point(const DevCamera &C, float3 p) {   // Transform::transformAffine (transform.h:128-136)
+    const float *t = C.c2w;
+    return mk3(t[0] * p.x + t[1] * p.y + t[2] * p.z + t[3], t[4] * p.x + t[5] * p.y + t[6] * p.z + t[7],
+               t[8] * p.x + t[9] * p.y + t[10] * p.z + t[11]);
+}
+
+// One camera ray of the thinlens sensor (ThinLens::sampleRayDifferential,
+// thinlens.cpp:324-361) for the sample at (x + a, y + b) and the aperture
+// sample (u, v): origin + mint, direction + maxt, and, with DIFFS, the
+// differential directions scaled by 1/sqrt(spp) as camera_differentials
+// scales the pinhole's (integrator.cpp:148-149, ray.h:163-168; rxOrigin =
+// ryOrigin = o, thinlens.cpp:355)
+template <bool DIFFS>
+DEV void lens_ray(const DevCamera &C, const DevIntegrator &I, int x, int y, float a, float b, float u, float v, float4 &ro, float4 &rd,
+                  float3 &rxs, float3 &rys) {
+    float tx, ty;
+    uniform_disk_concentric(u, v, tx, ty);
+    const float3 apertureP = mk3(tx * C.aperture_radius, ty * C.aperture_radius, 0.0f);
+    const float3 nearP = camera_near(C, x, y, a, b);
+    const float fDist = C.focus_distance / nearP.z;
+    const float3 d = normalize(nearP * fDist - apertureP);
+    const float invZ = 1.0f / d.z;
+    const float3 o = camera_to_world_point(C, apertureP), wd = camera_to_world_dir(C, d);
+    ro = make_float4(o.x, o.y, o.z, C.near_clip * invZ);
+    rd = make_float4(wd.x, wd.y, wd.z, C.far_clip * invZ);
+    if (DIFFS) {
+        const float3 rx = camera_to_world_dir(C, normalize((nearP + ld3(C.dx)) * fDist - apertureP));
+        const float3 ry = camera_to_world_dir(C, normalize((nearP + ld3(C.dy)) * fDist - apertureP));
+        const float scale = 1.0f / sqrtf((float)I.spp);
+        rxs = wd + (rx - wd) * scale;
+        rys = wd + (ry - wd) * scale;
+    }
+}
+
+// k_camera of a thinlens scene.  The aperture sample is the sample's second
+// 2D request (integrator.cpp:178-186: dimensions 2-3, so bounce 0 starts at
+// dimension 4, camera_meta); the ray keeps its own origin, so it is stored
+// like a two-level scene's (ray_o / ray_d, DevScene::camCompact = 0), and
+// its differentials are always carried (DevScene::cam_diffs), never recomputed
+__global__ void __launch_bounds__(BLOCK) k_camera_lens(DevCamera C, DevIntegrator I, DevBatch B, DevPaths P) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= B.nslots) return;
+    int x, y;
+    uint32_t s;
+    slot_pixel(B, slot, x, y, s);
+    if (x < B.rect_x + B.rect_w && y < B.rect_y + B.rect_h) {
+        PathSampler p = path_sampler(I, x, y, s, 0, 0);
+        float a, b, u, v;
+        switch (I.smp.type) {
+            case MTSG_SAMPLER_HALTON: next2D<MTSG_SAMPLER_HALTON>(I, p, a, b); next2D<MTSG_SAMPLER_HALTON>(I, p, u, v); break;
+            case MTSG_SAMPLER_HAMMERSLEY: next2D<MTSG_SAMPLER_HAMMERSLEY>(I, p, a, b); next2D<MTSG_SAMPLER_HAMMERSLEY>(I, p, u, v); break;
+            case MTSG_SAMPLER_LDSAMPLER: next2D<MTSG_SAMPLER_LDSAMPLER>(I, p, a, b); next2D<MTSG_SAMPLER_LDSAMPLER>(I, p, u, v); break;
+            case MTSG_SAMPLER_SOBOL: next2D<MTSG_SAMPLER_SOBOL>(I, p, a, b); next2D<MTSG_SAMPLER_SOBOL>(I, p, u, v); break;
+            default: next2D<MTSG_SAMPLER_INDEPENDENT>(I, p, a, b); next2D<MTSG_SAMPLER_INDEPENDENT>(I, p, u, v); break;
+        }
+        float4 ro, rd;
+        float3 rxs, rys;
+        if (C.diffs) {
+            lens_ray<true>(C, I, x, y, a, b, u, v, ro, rd, rxs, rys);
+            // parked in T and aux until bounce 0 is shaded, as k_camera's
+            stS(&P.T[slot], make_float4(rxs.x, rxs.y, rxs.z, 1.f));
+            stS(&P.aux[slot], make_float4(rys.x, rys.y, rys.z, 0.f));
+        } else {
+            lens_ray<false>(C, I, x, y, a, b, u, v, ro, rd, rxs, rys);
+        }
+        stS(&P.ray_o[slot], ro);
+        stS(&P.ray_d[slot], rd);
+    } else {
+        // dead slot, as k_camera's: a negative maxt
+        stS(&P.ray_o[slot], make_float4(0.f, 0.f, 0.f, 0.f));
+        stS(&P.ray_d[slot], make_float4(0.f, 0.f, 1.f, -1.0f));
+        stS(&P.L[slot], make_float4(0.f, 0.f, 0.f, 0.f));
     }
 }
 

@@ -352,7 +352,8 @@ ShadeLaunch shade_args(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B,
 }
 // where bounce 0 finds the camera rays' differentials (mtsg_scene::storeCamDiffs)
 void camera_diff_mode(mtsg_scene *s) {
-    s->ds.cam_diffs = (s->texDiffs || (s->hasEnvmap && s->storeCamDiffs)) ? 1 : 0;
+    // (a thinlens ray's differentials depend on its aperture sample: always carried)
+    s->ds.cam_diffs = (s->texDiffs || (s->hasEnvmap && (s->storeCamDiffs || s->cam.lens))) ? 1 : 0;
     s->ds.cam_env_diffs = (s->hasEnvmap && !s->ds.cam_diffs) ? 1 : 0;
     s->cam.diffs = s->ds.cam_diffs;
 }
@@ -622,7 +623,7 @@ struct RenderRun {
     DevBatch dev_batch(const PlanBatch &b) const {   // (in DevBatch's field order)
         return DevBatch{p->tile_x, p->tile_y, p->tile_w, p->tile_h, (int)plan.tilesX, (int)b.tile0, (int)b.ntiles,
                         (int)plan.tstride, (int)plan.toffset, PLAN_DEAL_SKEW, b.s0, b.ns, b.nslots,
-                        s->tileKeys.empty() ? nullptr : s->tileKeysDev};
+                        s->tileKeys.empty() ? nullptr : s->tileKeysDev, s->cam.lens ? 1u : 0u};
     }
     DirectLaunch direct_args(uint32_t l) const {
         return DirectLaunch{s->lstream[l], &s->ds, &I, &lane[l].B, &s->LP[l], &s->fan, s->cam.has_alpha, (s->ds.has_env & 1) != 0, s->extBsdfs,
@@ -681,7 +682,9 @@ struct RenderRun {
         if (b == 0) {
             HIP_TRY(hipMemsetAsync(P.cnt, 0, CNT_WORDS * sizeof(uint32_t), st));
             timed_launch(s, K_CAMERA, st, [&]() {
-                hipLaunchKernelGGL(k_camera, dim3((L.B.nslots + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, s->cam, I, L.B, P);
+                const dim3 g((L.B.nslots + BLOCK - 1) / BLOCK);
+                if (s->cam.lens) hipLaunchKernelGGL(k_camera_lens, g, dim3(BLOCK), 0, st, s->cam, I, L.B, P);
+                else hipLaunchKernelGGL(k_camera, g, dim3(BLOCK), 0, st, s->cam, I, L.B, P);
             });
         }
         const int qin = b == 0 ? -1 : (b & 1);
@@ -1133,6 +1136,17 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
         return MTSG_ERR_INVALID;
     }
     if (d->camera.border > MAX_BORDER) { g_err = "reconstruction filter radius too large (border > 4)"; return MTSG_ERR_INVALID; }
+    if (d->camera.sensor_type != MTSG_SENSOR_PERSPECTIVE && d->camera.sensor_type != MTSG_SENSOR_THINLENS) {
+        g_err = "unknown sensor type";
+        return MTSG_ERR_INVALID;
+    }
+    if (d->camera.sensor_type == MTSG_SENSOR_THINLENS) {
+        if (!(d->camera.aperture_radius > 0) || !(d->camera.focus_distance > 0)) {
+            g_err = "thinlens sensor: aperture_radius and focus_distance must be > 0";
+            return MTSG_ERR_INVALID;
+        }
+        if (d->om) { g_err = "myPath2_OM scenes take the perspective sensor only"; return MTSG_ERR_INVALID; }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
         g_err = "no such HIP device";
@@ -1611,9 +1625,11 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
     memcpy(c.dx, hc.dx, sizeof(c.dx));
     memcpy(c.dy, hc.dy, sizeof(c.dy));
     c.crop_w = hc.crop_w; c.crop_h = hc.crop_h;
+    c.lens = hc.sensor_type == MTSG_SENSOR_THINLENS ? 1 : 0;
+    c.aperture_radius = hc.aperture_radius; c.focus_distance = hc.focus_distance;
     ds.camO[0] = c.c2w[3]; ds.camO[1] = c.c2w[7]; ds.camO[2] = c.c2w[11];
     ds.camNear = c.near_clip; ds.camFar = c.far_clip;
-    ds.camCompact = ds.inst ? 0 : 1;
+    ds.camCompact = (ds.inst || c.lens) ? 0 : 1;   // (a thinlens ray starts on the aperture: k_camera_lens)
     c.compact = ds.camCompact;
     camera_diff_mode(s);
     // the camera on the device too: bounce 0 recomputes a missing camera ray's
@@ -2213,6 +2229,23 @@ __global__ void k_sampler_draws(DevIntegrator I, DevArrays A, int x, int y, uint
     }
     *err = p.dimError ? 1 : 0;
 }
+
+// mtsg_camera_rays: the camera rays of the listed slots as bounce 0 reads
+// them (load_closest_ray), and the differentials k_camera parked in T / aux
+__global__ void k_camera_rays_read(DevScene S, DevPaths P, const uint32_t *slots, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t slot = slots[i];
+    float4 ro, rd;
+    load_closest_ray(S, P, slot, P.camEnc != 0, ro, rd);
+    const float4 rx = ldS(&P.T[slot]), ry = ldS(&P.aux[slot]);
+    float *o = out + (size_t)14 * i;
+    o[0] = ro.x; o[1] = ro.y; o[2] = ro.z;
+    o[3] = rd.x; o[4] = rd.y; o[5] = rd.z;
+    o[6] = ro.w; o[7] = rd.w;
+    o[8] = rx.x; o[9] = rx.y; o[10] = rx.z;
+    o[11] = ry.x; o[12] = ry.y; o[13] = ry.z;
+}
 }  // namespace
 
 extern "C" {
@@ -2262,6 +2295,70 @@ int mtsg_sampler_draws(mtsg_scene *s, const mtsg_render_params *p, int x, int y,
         g_err = dim_error(s->samplerType);
         return MTSG_ERR_INVALID;
     }
+    return MTSG_OK;
+}
+
+int mtsg_camera_rays(mtsg_scene *s, const mtsg_render_params *p, uint32_t n, const int32_t *xys, float *out) {
+    if (!s || (n && (!xys || !out))) { g_err = "invalid arguments"; return MTSG_ERR_INVALID; }
+    int rc;
+    if ((rc = validate(p, s)) != MTSG_OK) return rc;
+    if (n == 0) return MTSG_OK;
+    if ((rc = set_device(s)) != MTSG_OK) return rc;
+    // one batch over the whole rectangle and every sample: k_camera's own launch
+    const uint32_t tilesX = (uint32_t)(p->tile_w + TILE - 1) / TILE, tilesY = (uint32_t)(p->tile_h + TILE - 1) / TILE;
+    const uint64_t nslots64 = (uint64_t)tilesX * tilesY * TILE * TILE * p->spp;
+    if (nslots64 > (1u << 22)) { g_err = "camera_rays: rectangle x spp exceeds 2^22 sample slots"; return MTSG_ERR_INVALID; }
+    const uint32_t nslots = (uint32_t)nslots64;
+    const DevBatch B{p->tile_x, p->tile_y, p->tile_w, p->tile_h, (int)tilesX, 0, (int)(tilesX * tilesY), 1, 0, PLAN_DEAL_SKEW,
+                     0u, p->spp, nslots, nullptr, s->cam.lens ? 1u : 0u};
+    // the slot of each (x, y, s): the inverse of slot_pixel
+    std::vector<uint32_t> tileOf((size_t)tilesX * tilesY), pixOf(TILE * TILE), slots(n);
+    for (uint32_t v = 0; v < tilesX * tilesY; ++v) {
+        int tx, ty;
+        tile_of_key((int)v, (int)tilesX, tx, ty, PLAN_DEAL_SKEW);
+        tileOf[(size_t)ty * tilesX + tx] = v;
+    }
+    for (uint32_t pix = 0; pix < TILE * TILE; ++pix) {
+        int lx, ly;
+        tile_pix(pix, lx, ly);
+        pixOf[ly * TILE + lx] = pix;
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const int x = xys[3 * i] - p->tile_x, y = xys[3 * i + 1] - p->tile_y, si = xys[3 * i + 2];
+        if (x < 0 || y < 0 || x >= p->tile_w || y >= p->tile_h || si < 0 || (uint32_t)si >= p->spp) {
+            g_err = "camera_rays: a sample lies outside the rectangle or the sample count";
+            return MTSG_ERR_INVALID;
+        }
+        const uint32_t v = tileOf[(size_t)(y / TILE) * tilesX + x / TILE];
+        slots[i] = ((v * p->spp + (uint32_t)si) * (TILE * TILE)) + pixOf[(y % TILE) * TILE + x % TILE];
+    }
+    DevIntegrator I{p->max_depth, p->rr_depth, p->strict_normals, p->hide_emitters, p->spp, p->seed, (uint32_t)s->cam.film_w,
+                    make_sampler(s, p->spp)};
+    I.om = p->integrator == MTSG_INTEGRATOR_PATH2_OM ? 1 : 0;
+    I.om_strategy = p->om_strategy;
+    I.om_mis = p->om_mis;
+    I.om_jitter = p->om_jitter;
+    DevCamera cam = s->cam;
+    cam.diffs = 1;   // the differentials too (myPath2_OM has none: zeros)
+    hipError_t e = hipSuccess;
+    DevBuf<float4> ro(e, nslots), rd(e, nslots), T(e, nslots), aux(e, nslots), L(e, nslots);
+    DevBuf<uint4> meta(e, nslots);
+    DevBuf<uint32_t> dslots(e, n, slots.data());
+    DevBuf<float> dout(e, (size_t)14 * n);
+    if (e == hipSuccess) e = hipMemsetAsync(T.p, 0, nslots * sizeof(float4), s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(aux.p, 0, nslots * sizeof(float4), s->stream);
+    if (e == hipSuccess) {
+        DevPaths P{};
+        P.ray_o = ro.p; P.ray_d = rd.p; P.T = T.p; P.aux = aux.p; P.L = L.p; P.meta = meta.p;
+        P.camEnc = s->ds.camCompact ? 1u : 0u;
+        const dim3 g((nslots + BLOCK - 1) / BLOCK);
+        if (cam.lens) hipLaunchKernelGGL(k_camera_lens, g, dim3(BLOCK), 0, s->stream, cam, I, B, P);
+        else hipLaunchKernelGGL(k_camera, g, dim3(BLOCK), 0, s->stream, cam, I, B, P);
+        hipLaunchKernelGGL(k_camera_rays_read, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, P, dslots.p, n, dout.p);
+        e = hipStreamSynchronize(s->stream);
+    }
+    dout.download(out);
+    if (e != hipSuccess) { g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
     return MTSG_OK;
 }
 

@@ -428,7 +428,10 @@ void Scene::finalize() {
             return (float)(2 * std::atan(width * 0.5) * 180.0 / M_PI);
         };
         if (fov < 0) {
-            xfov = fromDiag((float)(2 * 180 / M_PI * std::atan(std::sqrt(36.0 * 36 + 24 * 24) / (2 * 50.0))));
+            // sensor.cpp:276 in its precisions: the float sqrt, quotient and
+            // atan, the double 2 * 180 / M_PI, a float on entry to setDiagonalFov
+            const float value = sensor.focalLength;
+            xfov = fromDiag((float)(2 * 180 / M_PI * std::atan(std::sqrt((float)(36 * 36 + 24 * 24)) / (2 * value))));
         } else {
             if (axis == "smaller") axis = aspect > 1 ? "y" : "x";
             else if (axis == "larger") axis = aspect > 1 ? "x" : "y";
@@ -461,6 +464,16 @@ void Scene::finalize() {
     cam.film_h = f.height;
     cam.crop_x = f.cropX; cam.crop_y = f.cropY; cam.crop_w = f.cropW; cam.crop_h = f.cropH;
     cam.has_alpha = f.hasAlpha ? 1 : 0;
+    // thinlens.cpp:122-143: the projection is the perspective camera's
+    // (thinlens.cpp:156-212 = perspective.cpp:126-176)
+    if (sensor.thinlens) {
+        if (integrator.type == "myPath2_OM")
+            throw std::runtime_error("myPath2_OM: the thinlens sensor is outside this build's scope (its paths start at the "
+                                     "camera's origin; use perspective)");
+        cam.sensor_type = MTSG_SENSOR_THINLENS;
+        cam.aperture_radius = sensor.apertureRadius;
+        cam.focus_distance = sensor.focusDistance;
+    }
     // myPath2_OM accumulates each pixel's running mean of its own samples
     // and hands the film a finished bitmap (myPath2_OM.cpp:229-281): a box of
     // exactly one pixel, no alpha

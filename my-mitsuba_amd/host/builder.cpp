@@ -17,13 +17,14 @@
 //   texture bitmap (bitmap.cpp:179-302)
 //   emitter area (area.cpp:67-78), envmap (envmap.cpp:105-185)
 //   shapes  ply, obj, serialized, cube, rectangle, shapegroup / instance
-//   sensor  perspective (perspective.cpp, sensor.cpp:150-262), film hdrfilm
+//   sensor  perspective, thinlens (perspective.cpp, thinlens.cpp:122-143, sensor.cpp:150-278), film hdrfilm
 //           (hdrfilm.cpp:209-220), rfilter gaussian / box
 //   sampler independent, halton, hammersley, ldsampler, sobol
 //   integrator path (integrator.cpp:199-234), myPath2_OM (myPath2_OM.cpp:61-85)
 #include <algorithm>
 #include <cctype>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 
@@ -933,18 +934,39 @@ void SceneBuilder::multichannel(const Properties &, int line) {
 
 void SceneBuilder::sensor(const std::string &type_, const Properties &props, int line) {
     const std::string type = lower(type_);
-    if (type != "perspective") throw err(at(line) + "sensor \"" + type + "\" is outside this build's scope");
-    Sensor &s = scene.sensor;
+    if (type != "perspective" && type != "thinlens")
+        throw err(at(line) + "sensor \"" + type + "\" is outside this build's scope (perspective, thinlens)");
+    Sensor s;
     s.present = true;
     s.toWorld = props.getTransform("toWorld", Transform());
+    // ProjectiveCamera (sensor.cpp:156-170)
     s.nearClip = props.getFloat("nearClip", 1e-2f);
     s.farClip = props.getFloat("farClip", 1e4f);
+    s.focusDistance = props.getFloat("focusDistance", s.farClip);
     if (s.nearClip <= 0) throw err("The 'nearClip' parameter must be greater than zero!");
     if (s.nearClip >= s.farClip) throw err("The 'nearClip' parameter must be smaller than 'farClip'.");
-    if (props.has("fov")) s.fov = props.getFloat("fov");
-    else if (props.strings.count("focalLength")) throw err("focalLength is not supported by this loader; use fov");
-    else s.fov = -1;  // default focal length 50mm handled in finalize
+    // PerspectiveCamera (sensor.cpp:220-229, 244-276)
+    if (props.has("fov") && props.has("focalLength"))
+        throw err("Please specify either a focal length ('focalLength') or a field of view ('fov')!");
+    if (props.has("fov")) {
+        s.fov = props.getFloat("fov");
+    } else {
+        s.fov = -1;   // the focal length's diagonal field of view: finalize
+        std::string f = props.getString("focalLength", "50mm");
+        if (f.size() >= 2 && f.compare(f.size() - 2, 2, "mm") == 0) f = f.substr(0, f.size() - 2);
+        char *end = nullptr;
+        s.focalLength = (float)strtod(f.c_str(), &end);
+        if (*end != '\0')
+            throw err("Could not parse the focal length (must be of the form <x>mm, where <x> is a positive integer)!");
+    }
     s.fovAxis = lower(props.getString("fovAxis", "x"));
+    if (type == "thinlens") {   // thinlens.cpp:124-143
+        s.thinlens = true;
+        s.apertureRadius = props.getFloat("apertureRadius");
+        if (s.apertureRadius == 0) s.apertureRadius = 1e-4f;   // Epsilon (constants.h)
+        if (hasScale(s.toWorld)) throw err("Scale factors in the camera-to-world transformation are not allowed!");
+    }
+    scene.sensor = s;
 }
 
 void SceneBuilder::sampler(const std::string &type, const Properties &sp) {

@@ -14,7 +14,7 @@
 //           (roughconductor.cpp:168-203, microfacet.h:99-146),
 //           dielectric (dielectric.cpp:148-170)
 //   emitter area (area.cpp:67-78)
-//   sensor  perspective (perspective.cpp, sensor.cpp:150-262)
+//   sensor  perspective, thinlens (perspective.cpp, thinlens.cpp:122-143, sensor.cpp:150-278)
 //   film    hdrfilm (hdrfilm.cpp:209-220), rfilter gaussian/box
 //   sampler independent (independent.cpp:55-58), halton (halton.cpp:113-121),
 //           hammersley (hammersley.cpp:93-101), ldsampler (ldsampler.cpp:82-95)

@@ -108,6 +108,11 @@ struct Sensor {
     float fov = -1;
     std::string fovAxis = "x";
     float nearClip = 1e-2f, farClip = 1e4f;
+    // without `fov`: the focal length in mm of a 35mm film (sensor.cpp:265-276)
+    float focalLength = 50.0f;
+    // thinlens (thinlens.cpp:122-143, sensor.cpp:162)
+    bool thinlens = false;
+    float apertureRadius = 0.0f, focusDistance = 0.0f;
     bool present = false;
 };
 

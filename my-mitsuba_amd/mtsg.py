@@ -308,7 +308,7 @@ DEVICE_SYMBOLS = [
     "mtsg_cancel", "mtsg_cancel_clear", "mtsg_set_flags", "mtsg_get_stats", "mtsg_set_batch_paths", "mtsg_set_finish_paths",
     "mtsg_trace_closest", "mtsg_trace_shadow", "mtsg_render_samples", "mtsg_scene_destroy",
     "mtsg_last_error", "mtsg_env_eval", "mtsg_tex_eval", "mtsg_om_query", "mtsg_kd_build", "mtsg_kd_refit", "mtsg_kd_free",
-    "mtsg_sampler_draws", "mtsg_debug_wavetimes", "mtsg_set_tile_callback",
+    "mtsg_sampler_draws", "mtsg_camera_rays", "mtsg_debug_wavetimes", "mtsg_set_tile_callback",
     "mtsg_debug_stragglers", "mtsg_set_test_knobs", "mtsg_set_option",
     "mtsg_scene_set_aov", "mtsg_render_multi", "mtsg_render_device_multi", "mtsg_render_device_tiles_multi",
     "mtsg_render_samples_multi", "mtsg_scene_set_direct", "mtsg_scene_kernel_sets",
@@ -492,6 +492,7 @@ def device_lib() -> C.CDLL:
         lib.mtsg_om_query.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mtsg_sampler_draws.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_int, C.c_int, C.c_uint32,
                                            C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.mtsg_camera_rays.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_uint32, C.c_void_p, C.c_void_p]
         lib.mtsg_scene_destroy.argtypes = [C.c_void_p]
         lib.mtsg_set_tile_callback.argtypes = [C.c_void_p, TILE_FN, C.c_void_p]
         lib.mtsg_set_test_knobs.argtypes = [C.c_void_p, C.POINTER(TestKnobs)]
@@ -1109,6 +1110,17 @@ class GPUScene:
         out = np.empty(int(np.where(kinds < 0, -2 * kinds, np.where(kinds == 2, 2, 1)).sum()), np.float32)
         self._check(device_lib().mtsg_sampler_draws(self._h, C.byref(params), x, y, s, kinds.size, _ptr(kinds), _ptr(out)),
                     "mtsg_sampler_draws")
+        return out
+
+    def camera_rays(self, params: RenderParams, xys) -> np.ndarray:
+        """The camera rays k_camera produces for the samples xys = (n, 3) of
+        (x, y, s) in film coordinates (debug entry point, mtsg_camera_rays):
+        (n, 14) = origin, direction, mint, maxt, then the x and y differential
+        directions scaled by 1/sqrt(spp)."""
+        xys = np.ascontiguousarray(xys, dtype=np.int32).reshape(-1, 3)
+        out = np.empty((xys.shape[0], 14), np.float32)
+        self._check(device_lib().mtsg_camera_rays(self._h, C.byref(params), xys.shape[0], _ptr(xys), _ptr(out)),
+                    "mtsg_camera_rays")
         return out
 
     def trace_shadow(self, rays: np.ndarray) -> np.ndarray:

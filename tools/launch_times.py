@@ -26,7 +26,7 @@ def last_frame(path):
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
     rows = [(short(r["Kernel_Name"]), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3) for r in rows
             if not r["Kernel_Name"].startswith("__amd")]
-    starts = [i for i, (n, _) in enumerate(rows) if n == "k_camera"]
+    starts = [i for i, (n, _) in enumerate(rows) if n in ("k_camera", "k_camera_lens")]
     return rows[starts[-1]:] if starts else rows
 
 
@@ -36,7 +36,7 @@ def main():
         label, path = arg.split("=", 1)
         runs.append((label, last_frame(path)))
     print("# per-launch durations (us) of the last frame, dispatch order; k_reset / copies omitted")
-    kinds = ("k_trace_s", "k_shade", "k_finish", "k_tie", "k_camera", "k_splat")
+    kinds = ("k_trace_s", "k_shade", "k_finish", "k_tie", "k_camera", "k_camera_lens", "k_splat")
     for label, rows in runs:
         print(f"## {label}")
         tot = {}
