@@ -690,7 +690,13 @@ int  mtsg_set_finish_paths(mtsg_scene *scene, uint32_t paths);
  *                             bounce 0, 1 = the camera stores them in the path
  *                             state (the layout through round 5; A/B tests).
  *                             Scenes with filtered textures always store them.
+ *   MTSG_OPT_RECT_SETUP       flat scenes: 1 (default) = the traversal tests the
+ *                             scene's rectangles once per ray at its setup, where
+ *                             the scene has few enough of them, 0 = in the kd-tree
+ *                             leaves, as every other traversal does (A/B tests)
  * Unknown keys and values out of range return MTSG_ERR_INVALID. */
+/* the most rectangles a flat scene may hold for MTSG_OPT_RECT_SETUP 1 to apply */
+#define MTSG_RECT_SETUP_CAP 2u
 enum {
     MTSG_OPT_TRACE_REFILL = 1,
     MTSG_OPT_FINISH_SHADE_MIN = 2,
@@ -698,7 +704,8 @@ enum {
     MTSG_OPT_STAGGER = 4,
     MTSG_OPT_SHADE_GENERIC = 5,
     MTSG_OPT_RAY_ORDER = 6,
-    MTSG_OPT_CAMERA_DIFFS = 7
+    MTSG_OPT_CAMERA_DIFFS = 7,
+    MTSG_OPT_RECT_SETUP = 8
 };
 int  mtsg_set_option(mtsg_scene *scene, int32_t key, int64_t value);
 

@@ -45,6 +45,10 @@ struct DevScene {
     // per rectangle its to_object rows as 3 float4 (48 B, the size of a
     // TriAccel record): MTSG_RECT_PEND reads them through the primitive slot
     const float4 *__restrict__ rectM;
+    // number of rectangles: the flat traversal's setup-mode kernels test all
+    // of them once per ray at its setup (spec_init<true>); rectangle r's
+    // TriAccel index, its tie key, is n_tri + r (checked at upload)
+    uint32_t n_rect;
     // per rectangle its shading data, 2 float4 (one fetch per hit instead of
     // the rectangle, then its shape): {frame_n, shape}, {dpdu, bsdf | (emitter + 1) << 16}
     const float4 *__restrict__ rectSh;
@@ -230,6 +234,7 @@ struct FlatTraceLaunch {
     uint32_t n;
     unsigned long long *wt;
     bool count, knobs, refill32, tie;
+    bool rectSetup;   // the setup-mode kernels (rectangles tested at ray setup); false: k_trace_s_leaf
 };
 void launch_trace_flat(const FlatTraceLaunch &a);
 int trace_flat_blocks_per_cu();   // k_trace_s<false, 16> workgroups per CU (occupancy query)
@@ -820,7 +825,29 @@ DEV float4 miss_record() {
 // adaptive epsilon of ShapeKDTree::rayIntersect / rayIntersect for shadow
 // rays (skdtree.cpp:112-142 / 207-226).  Returns false when the ray misses
 // the scene bounds or its interval is empty.
-DEV bool spec_init(const DevScene &S, float3 o, float3 d, float rayMint, float rayMaxt, bool shadow, SpecRay &r) {
+//
+// RS (rectangles at setup, the production flat kernels): every rectangle of
+// the scene is tested here, once per ray, as if they all sat in one extra leaf
+// visited first, in index order, and spec_iter<.., RS = true> skips rectangle
+// records in the leaves.  A scene has a handful of rectangles but most rays
+// meet one (a ground plane, an area light), so with ~50 busy lanes nearly
+// every wave-iteration ran the in-leaf test -- 58 VALU, three dependent loads
+// and a wait of their own -- for one or two lanes; here it runs for the 16 or
+// more lanes of a refill, on rows at wave-uniform addresses.  The same
+// rect_test_m arithmetic on the same r.mint / r.best and the same acceptance,
+// so t, u, v are the leaf test's; the closest hit is the minimum over accepted
+// candidates in either order; and the order decides the winner only at an
+// exact tie, which is flagged by the same rule as in spec_iter (whichever of
+// the two is tested second sees t == r.best with another key) and retraced by
+// k_tie in Mitsuba's order.  tmin / tmax are not shrunk: the descent is the
+// one the in-leaf mode takes, only Havran's exit can come sooner.
+// A closest ray's best rectangle is written to hitOut; a shadow ray that hits
+// a rectangle is occluded: false with SB_FOUND in r.bits (false otherwise
+// leaves r.bits 0), the caller does nothing more for it.
+template <bool RS = false>
+DEV bool spec_init(const DevScene &S, float3 o, float3 d, float rayMint, float rayMaxt, bool shadow, SpecRay &r,
+                   float4 *hitOut = nullptr) {
+    if (RS) r.bits = 0u;
     r.o = o;
     r.d = d;
     r.inv = mk3(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
@@ -855,6 +882,32 @@ DEV bool spec_init(const DevScene &S, float3 o, float3 d, float rayMint, float r
     r.mb = 0;
     r.bestKey = 0xFFFFFFFFu;   // no best yet (a first hit exactly at a finite maxt is flagged
                               // and traced again with the mailbox: the same answer)
+    if (RS) {
+        // a uniform trip count and selects: no exec-mask branches in the loop
+        // (a shadow ray keeps its interval: any hit occludes, in any order)
+        float4 rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        bool found = false;
+        const uint32_t nR = S.n_rect;
+        for (uint32_t k = 0; k < nR; ++k) {
+            const float4 *m = S.rectM + 3u * k;   // wave-uniform
+            float t, u, v;
+            const bool h = rect_test_rows(m[0], m[1], m[2], r.o, r.d, r.mint, r.best, t, u, v);
+            const uint32_t key = S.n_tri + k;
+            r.bits |= (h & (t == r.best) & (key != r.bestKey)) ? SB_TIE : 0u;
+            r.bestKey = h ? key : r.bestKey;
+            r.best = (h & !shadow) ? t : r.best;
+            rec = h ? make_float4(t, u, v, __uint_as_float(0x80000000u | k)) : rec;
+            found |= h;
+        }
+        if (found) {
+            if (shadow) {
+                r.bits = SB_FOUND;
+                return false;
+            }
+            r.bits |= SB_FOUND;
+            stS(hitOut, rec);
+        }
+    }
     return true;
 }
 
@@ -969,6 +1022,17 @@ constexpr bool TIE_INLINE = MTSG_TIE_INLINE;
 #define MTSG_RETIRE_BATCH 1
 #endif
 constexpr bool RETIRE_BATCH = MTSG_RETIRE_BATCH;
+// k_trace_s, flat scenes: the production instantiations test the scene's
+// rectangles once per ray at its setup instead of in the leaves
+// (spec_init<true>).  0: in the leaves everywhere, as through round 7.
+#ifndef MTSG_RECT_SETUP
+#define MTSG_RECT_SETUP 1
+#endif
+constexpr bool RECT_SETUP = MTSG_RECT_SETUP && !MTSG_RECT_PEND && !MTSG_TIE_INLINE;
+// scenes with more rectangles keep the in-leaf test: every ray pays for every
+// rectangle at its setup, in a leaf only for those it passes (include/mtsg.h
+// MTSG_RECT_SETUP_CAP)
+constexpr uint32_t RECT_SETUP_CAP = MTSG_RECT_SETUP_CAP;
 __shared__ uint32_t s_mbPrev[TRACE_BLOCK];
 // the tie branch of mailbox_step (mb: the state before this test)
 DEV bool mailbox_tie(SpecRay &r, uint32_t mb, uint32_t sl, uint32_t id, const float4 *hitOut) {
@@ -1001,8 +1065,13 @@ DEV bool mailbox_step(SpecRay &r, uint32_t key, bool isRect, uint32_t prim, bool
     return h;
 }
 
-template <bool COUNT, bool MB = false>
+// RS: the ray tested the scene's rectangles at its setup (spec_init<true>);
+// rectangle records in the leaves are stepped over, and the rectangle test and
+// its loads are not compiled into the iteration.  Only k_trace_s's production
+// flat instantiations: every other caller visits primitives in Mitsuba's order.
+template <bool COUNT, bool MB = false, bool RS = false>
 DEV bool spec_iter(const DevScene &S, SpecRay &r, SpecStack stk, TraceCounts &cnt, float4 *hitOut, const TravLimits &L) {
+    static_assert(!(RS && (MB || MTSG_RECT_PEND)), "the mailbox retrace and MTSG_RECT_PEND test rectangles in the leaves");
     const uint2 n = r.cur;
     const bool inner = !(r.bits & SB_TRAVDONE) && !(n.x & 0x80000000u);
     const bool prim = r.lfE < r.lfEnd;
@@ -1061,10 +1130,14 @@ DEV bool spec_iter(const DevScene &S, SpecRay &r, SpecStack stk, TraceCounts &cn
         }
 #else
     if (prim) {
-        if (COUNT) { cnt.refs++; cnt.tests++; }
+        // RS: a rectangle record is a leaf reference, not a test -- the ray
+        // tested every rectangle at its setup (spec_init<true>), and
+        // tri_test rejects the record (k = MTSG_TRIACCEL_SHAPE is no axis),
+        // so the lane only steps over it
+        if (COUNT) { cnt.refs++; cnt.tests += !(RS && __float_as_uint(f0.x) == MTSG_TRIACCEL_SHAPE); }
         float t, u, v;
         bool h = tri_test(f0, f1, f2, r.o, r.d, r.mint, r.best, u, v, t);
-        const bool isRect = __float_as_uint(f0.x) == MTSG_TRIACCEL_SHAPE;
+        const bool isRect = !RS && __float_as_uint(f0.x) == MTSG_TRIACCEL_SHAPE;
         if (isRect) h = rect_test(S.rects[__float_as_uint(f2.w)], r.o, r.d, r.mint, r.best, t, u, v);
         const uint32_t key = __float_as_uint(f2.z), pid = __float_as_uint(f2.w);
 #endif
@@ -1887,10 +1960,15 @@ DEV uint32_t shuffle_index(uint32_t x, uint32_t n) {
 
 // (the kernel's body: k_trace_s below, and under MTSG_FLAT_REGS its flat
 // specialisations with their own register budget in trace_flat.hip)
-template <bool COUNT, int MIN_IDLE, bool INST, bool KNOBS>
+template <bool COUNT, int MIN_IDLE, bool INST, bool KNOBS, bool LEAF_RECTS = false>
 DEV void trace_s_body(const DevScene &S, const DevPaths &P, int cIn, int sIn, uint32_t nIdentity, unsigned long long *wt) {
     const SpecStack stk{};
     const TravLimits L = trav_limits<KNOBS>(S);
+    // rectangles tested at ray setup, not in the leaves (spec_init<true>):
+    // the production flat kernels; not the test knobs' kernel, and not
+    // k_trace_s_leaf (LEAF_RECTS), the kernel of the scenes that keep the
+    // in-leaf test
+    constexpr bool RS = RECT_SETUP && !INST && !KNOBS && !LEAF_RECTS;
     lds_top_init(S);
     const unsigned long long tStart = wt ? wall_clock64() : 0ull;
     const uint32_t nC = cIn == -1 ? nIdentity : (cIn >= 0 ? __atomic_load_n(&P.cnt[cnt_q(cIn)], __ATOMIC_RELAXED) : 0u);
@@ -1991,13 +2069,15 @@ DEV void trace_s_body(const DevScene &S, const DevPaths &P, int cIn, int sIn, ui
                 } else {
                     load_closest_ray(S, P, idx, !INST && P.camEnc != 0, ro, rd);   // (two-level scenes: never compact)
                 }
-                if (spec_init(S, xyz(ro), xyz(rd), ro.w, rd.w, shadow, r)) {
+                if (spec_init<RS>(S, xyz(ro), xyz(rd), ro.w, rd.w, shadow, r, P.hit + idx)) {
                     active = true;
                     if (COUNT) {
                         iters = 0;
                         const TraceCounts &k = shadow ? cs : cc;
                         n0 = k.nodes; t0c = k.tests; r0 = k.restarts;
                     }
+                } else if (RS && (r.bits & SB_FOUND)) {
+                    // a shadow ray a rectangle occludes: nothing to write
                 } else if (shadow) {
                     shadow_unoccluded(P, idx);
                 } else if (!(rd.w < 0.0f)) {   // maxt < 0: dead slot outside the render rectangle
@@ -2034,8 +2114,8 @@ DEV void trace_s_body(const DevScene &S, const DevPaths &P, int cIn, int sIn, ui
                 // the retrace of a tie (below): Mitsuba's mailbox emulated (not counted)
                 done = spec_iter<false, true>(S, r, stk, cc, P.hit + idx, L);
             } else {
-                if (COUNT && (r.bits & SB_SHADOW)) done = spec_iter<COUNT>(S, r, stk, cs, P.hit + idx, L);
-                else done = spec_iter<COUNT>(S, r, stk, cc, P.hit + idx, L);
+                if (COUNT && (r.bits & SB_SHADOW)) done = spec_iter<COUNT, false, RS>(S, r, stk, cs, P.hit + idx, L);
+                else done = spec_iter<COUNT, false, RS>(S, r, stk, cc, P.hit + idx, L);
             }
         }
         if (COUNT && active) ++iters;
@@ -2101,6 +2181,16 @@ __global__ void __launch_bounds__(TRACE_BLOCK)
 __attribute__((amdgpu_waves_per_eu(INST ? (COUNT ? 1 : MTSG_INST_WAVES) : (MTSG_FLAT_REGS && !COUNT ? 0 : MTSG_SPEC_WAVES))))   // (0: no attribute)
 k_trace_s(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned long long *wt) {
     trace_s_body<COUNT, MIN_IDLE, INST, KNOBS>(S, P, cIn, sIn, nIdentity, wt);
+}
+// The flat traversal with the rectangles tested in the leaves, as
+// k_trace_s<COUNT, MIN_IDLE, false, false> was before the setup mode (the same
+// body, the compile-time limits): flat scenes with more rectangles than
+// MTSG_RECT_SETUP_CAP, and MTSG_OPT_RECT_SETUP 0.  Not the KNOBS instantiation:
+// its run-time limits cost C2 0.5 ms of 62.4 (profiles/rect_setup_ab.txt).
+template <bool COUNT, int MIN_IDLE>
+__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(MTSG_SPEC_WAVES)))
+k_trace_s_leaf(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned long long *wt) {
+    trace_s_body<COUNT, MIN_IDLE, false, false, true>(S, P, cIn, sIn, nIdentity, wt);
 }
 
 // ---------------------------------------------------------------------------

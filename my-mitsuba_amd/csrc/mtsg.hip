@@ -134,6 +134,11 @@ struct mtsg_scene {
     float *dumpL = nullptr;
     std::atomic<int> cancel{0};
     bool knobs = false;   // traversal test overrides set (mtsg_set_test_knobs): KNOBS kernels, no tail mode
+    // flat scenes: k_trace_s tests the rectangles once per ray at its setup
+    // (kernels.h spec_init<true>) when the option is on (MTSG_OPT_RECT_SETUP)
+    // and the scene can take it (at most RECT_SETUP_CAP rectangles, keyed
+    // n_triangles + index); else the kernels that test them in the leaves
+    bool rectSetupOpt = true, rectSetupOk = false;
     mtsg_stats stats{};
     std::vector<hipEvent_t> evPool;
     size_t evUsed = 0;
@@ -313,7 +318,7 @@ void launch_trace_c(mtsg_scene *s, const DevPaths &P, int cIn, int sIn, uint32_t
     const dim3 tg(std::max<unsigned>(1u, (unsigned)s->traceGrid / 4u));
     if (!s->ds.inst) {   // the flat kernels: trace_flat.hip
         FlatTraceLaunch a{g, tg, st, &s->ds, &P, cIn, sIn, n, wt, COUNT, s->knobs, s->traceMode == 1,
-                          MTSG_MAILBOX && cIn != -2 && !TIE_INLINE};
+                          MTSG_MAILBOX && cIn != -2 && !TIE_INLINE, s->rectSetupOpt && s->rectSetupOk};
         launch_trace_flat(a);
         return;
     }
@@ -1611,6 +1616,15 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
     }
     ds.n_emitters = d->n_emitters;
     ds.n_tri = d->n_triangles;
+    ds.n_rect = d->n_rects;
+    // the setup mode names rectangle r by the tie key n_triangles + r, its
+    // TriAccel index in the leaf records: hold the description to that
+    s->rectSetupOk = MTSG_RECT_SETUP && d->n_rects <= RECT_SETUP_CAP;
+    for (uint32_t r = 0; r < d->n_rects && s->rectSetupOk; ++r) {
+        const mtsg_triaccel &ta = d->triaccel[d->n_triangles + r];
+        s->rectSetupOk = ta.k == MTSG_TRIACCEL_SHAPE && ta.prim_index == r && ta.shape_index < d->n_shapes &&
+                         d->shapes[ta.shape_index].type == MTSG_SHAPE_RECT;
+    }
     ds.n_bsdfs = d->n_bsdfs;
     for (int k = 0; k < 3; ++k) { ds.bmin[k] = d->aabb_min[k]; ds.bmax[k] = d->aabb_max[k]; }
     DevCamera &c = s->cam;
@@ -1798,6 +1812,10 @@ int mtsg_set_option(mtsg_scene *s, int32_t key, int64_t value) {
             if (value < 0 || value > 1) { g_err = "MTSG_OPT_CAMERA_DIFFS: 0 (recomputed on a miss) or 1 (stored)"; return MTSG_ERR_INVALID; }
             s->storeCamDiffs = value != 0;
             camera_diff_mode(s);
+            return MTSG_OK;
+        case MTSG_OPT_RECT_SETUP:
+            if (value < 0 || value > 1) { g_err = "MTSG_OPT_RECT_SETUP: 0 (rectangles tested in the leaves) or 1 (at ray setup)"; return MTSG_ERR_INVALID; }
+            s->rectSetupOpt = value != 0;
             return MTSG_OK;
         default:
             g_err = "unknown option key " + std::to_string(key);

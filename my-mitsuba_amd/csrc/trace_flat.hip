@@ -33,7 +33,13 @@ namespace mtsg {
 template <bool COUNT>
 static void launch_flat(const FlatTraceLaunch &a) {
     const dim3 blk(TRACE_BLOCK);
+    // k_trace_s<.., false, false>: rectangles tested at ray setup (kernels.h
+    // spec_init<true>); <.., false, true>, the test knobs' kernel, and
+    // k_trace_s_leaf, the kernel of the scenes that do not take the setup mode
+    // (a.rectSetup false): in the leaves.  The COUNT pass follows the timed kernel.
     if (a.knobs && !COUNT) hipLaunchKernelGGL((k_trace_s<false, 16, false, true>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
+    else if (!a.rectSetup && a.refill32) hipLaunchKernelGGL((k_trace_s_leaf<COUNT, 32>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
+    else if (!a.rectSetup) hipLaunchKernelGGL((k_trace_s_leaf<COUNT, 16>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
     else if (a.refill32) hipLaunchKernelGGL((k_trace_s<COUNT, 32>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
     else hipLaunchKernelGGL((k_trace_s<COUNT, 16>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
     if (a.tie) {
