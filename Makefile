@@ -50,7 +50,7 @@ DEV_FLAGS := -O3 -std=c++17 -fPIC -Wall -ffp-contract=off -fno-slp-vectorize -mu
 # -0.6%; the two-level kernel in mtsg.hip loses 3% under it: DESIGN §3)
 DEV_FLAT_FLAGS ?= -mllvm -amdgpu-sched-strategy=max-memory-clause
 DEV_OBJ   ?= build/dev
-DEV_OBJS  := $(DEV_OBJ)/mtsg.o $(DEV_OBJ)/trace_flat.o $(DEV_OBJ)/fields.o $(DEV_OBJ)/direct.o $(DEV_OBJ)/kdbuild.o $(foreach k,0 1 2 3 4,$(DEV_OBJ)/smp_$(k).o)
+DEV_OBJS  := $(DEV_OBJ)/mtsg.o $(DEV_OBJ)/trace_flat.o $(DEV_OBJ)/fields.o $(DEV_OBJ)/direct.o $(DEV_OBJ)/direct2.o $(DEV_OBJ)/kdbuild.o $(foreach k,0 1 2 3 4,$(DEV_OBJ)/smp_$(k).o $(DEV_OBJ)/smp2_$(k).o)
 $(DEV_OBJ)/mtsg.o: $(PKG)/csrc/mtsg.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
@@ -65,12 +65,21 @@ $(DEV_OBJ)/fields.o: $(PKG)/csrc/fields.hip $(DEV_HDR)
 $(DEV_OBJ)/direct.o: $(PKG)/csrc/direct.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
+# ... and the same kernels for scenes with a BSDF type above roughplastic (EXT level 2)
+$(DEV_OBJ)/direct2.o: $(PKG)/csrc/direct.hip $(DEV_HDR)
+	@mkdir -p $(DEV_OBJ)
+	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -DMTSG_TU_EXT2 -c -o $@ $<
 $(DEV_OBJ)/kdbuild.o: $(PKG)/csrc/kdbuild.hip include/mtsg.h
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
 $(DEV_OBJ)/smp_%.o: $(PKG)/csrc/smp_kernels.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -DMTSG_TU_SAMPLER=$* $(if $(filter 0,$*),-DMTSG_TU_OCCUPANCY) -c -o $@ $<
+# the same sampler's kernels for scenes with a phong, ward, roughdiffuse,
+# difftrans or thindielectric record (EXT level 2), in units of their own
+$(DEV_OBJ)/smp2_%.o: $(PKG)/csrc/smp_kernels.hip $(DEV_HDR)
+	@mkdir -p $(DEV_OBJ)
+	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -DMTSG_TU_SAMPLER=$* -DMTSG_TU_EXT2 -c -o $@ $<
 # the objects are intermediates: a tree that carries the library without them
 # (a copy that leaves object files out) is current, not stale
 .SECONDARY: $(DEV_OBJS)

@@ -129,14 +129,34 @@ enum {
     MTSG_BSDF_CONDUCTOR      = 4,   /* src/bsdfs/conductor.cpp      */
     MTSG_BSDF_PLASTIC        = 5,   /* src/bsdfs/plastic.cpp        */
     MTSG_BSDF_ROUGHDIELECTRIC = 6,  /* src/bsdfs/roughdielectric.cpp */
-    MTSG_BSDF_ROUGHPLASTIC   = 7    /* src/bsdfs/roughplastic.cpp   */
+    MTSG_BSDF_ROUGHPLASTIC   = 7,   /* src/bsdfs/roughplastic.cpp   */
+    /* the stand-alone models below live in the widest shading kernels only
+     * (mtsg_scene_kernel_sets: material_set + 32) */
+    MTSG_BSDF_PHONG          = 8,   /* src/bsdfs/phong.cpp          */
+    MTSG_BSDF_WARD           = 9,   /* src/bsdfs/ward.cpp           */
+    MTSG_BSDF_ROUGHDIFFUSE   = 10,  /* src/bsdfs/roughdiffuse.cpp   */
+    MTSG_BSDF_DIFFTRANS      = 11,  /* src/bsdfs/difftrans.cpp      */
+    MTSG_BSDF_THINDIELECTRIC = 12   /* src/bsdfs/thindielectric.cpp */
 };
+enum { MTSG_WARD_WARD = 0, MTSG_WARD_DUER = 1, MTSG_WARD_BALANCED = 2 };   /* ward.cpp:89-95 (EModelVariant) */
 enum { MTSG_MF_BECKMANN = 0, MTSG_MF_GGX = 1, MTSG_MF_PHONG = 2 };   /* microfacet.h:49-57 */
 
 /* One BSDF record.  `twosided` (src/bsdfs/twosided.cpp) marks the record
  * of a twosided wrapper's front material: when the incident direction is on
  * the back (cosTheta(wi) <= 0 for eval/pdf, < 0 for sampling) the record
  * bsdfs[back] is used with wi.z and wo.z negated. */
+/* What the fields hold for the types 8..12 (every other field is zero):
+ *   phong          reflectance = diffuseReflectance, spec_refl =
+ *                  specularReflectance (both after the pair form of
+ *                  ensureEnergyConservation), alpha_u = exponent,
+ *                  spec_sampling_weight = sAvg / (dAvg + sAvg)
+ *   ward           as phong, with alpha_u / alpha_v = alphaU / alphaV (not
+ *                  clamped) and distribution = MTSG_WARD_* (the variant)
+ *   roughdiffuse   reflectance, alpha_u = alpha, nonlinear = useFastApprox
+ *   difftrans      reflectance = transmittance
+ *   thindielectric ior_eta = intIOR / extIOR, ior_inv_eta, spec_refl,
+ *                  spec_trans
+ * `texture` may name a bitmap for the parameter held in `reflectance`. */
 #define MTSG_RTRANS_SAMPLES 100     /* m_thetaSamples of the data/microfacet tables */
 
 typedef struct mtsg_bsdf {
@@ -714,7 +734,9 @@ int  mtsg_set_option(mtsg_scene *scene, int32_t key, int64_t value);
  * kernels).  *material_set = the material classes compiled in (1 diffuse,
  * 2 roughconductor GGX, 4 other roughconductor, 8 dielectric; 15 = every
  * class, also after MTSG_OPT_SHADE_GENERIC), + 16 when the scene holds one of
- * the other BSDF plugins; *emitter_set = MTSG_EMITTER_SET_*: the scene's
+ * the other BSDF plugins, + 32 when it holds a type above MTSG_BSDF_ROUGHPLASTIC
+ * (such a scene runs the "all kinds" kernels of its own, whatever its
+ * emitters); *emitter_set = MTSG_EMITTER_SET_*: the scene's
  * emitter kinds.  A scene with a point, spot, directional or constant emitter
  * runs the "all kinds" kernels (generic materials); every other scene runs
  * the kernels it ran before those kinds existed. */
@@ -755,6 +777,25 @@ int  mtsg_env_eval(mtsg_scene *scene, uint32_t n, const float *dirs, const float
  * with the uv partials duv = (d0.x, d0.y, d1.x, d1.y) per point, or the
  * unfiltered evalBilinear(0) / evalBox(0) when duv is NULL.  RGB out. */
 int  mtsg_tex_eval(mtsg_scene *scene, int tex, uint32_t n, const float *uv, const float *duv, float *out);
+
+/* Debug / parity entry: BSDF::sample(bRec, pdf, sample), BSDF::eval(bRec) and
+ * BSDF::pdf(bRec) (include/mitsuba/render/bsdf.h:347-395, ESolidAngle,
+ * ERadiance, every component) of record `bsdf`, through the bsdf_sample /
+ * bsdf_eval the shading kernels call.  alb: NULL, or n x rgb, the value the
+ * shading kernels would pass for the textured parameter at each query (a
+ * bitmap's value at the hit, mtsg_tex_eval x the texture's scale); NULL takes
+ * the constant of the record that answers.  A twosided front record hands
+ * back-side queries to its back record, as in a render.
+ * MTSG_BSDF_QUERY_SAMPLE: in = n x {wi.xyz, sample.x, sample.y, u}, u being
+ * what the sampler's next1D returns where the model draws it (roughdielectric);
+ * out = n x {wo.xyz, weight.rgb, pdf, eta}, flags = n x MTSG_BSDF_QUERY_* bits
+ * (a failed sample, i.e. a zero weight, has flags 0 and zeros in out).
+ * MTSG_BSDF_QUERY_EVAL: in = n x {wi.xyz, wo.xyz}, out = n x {eval * cos
+ * (rgb), pdf}; flags may be NULL.  Both are zero for the delta components. */
+enum { MTSG_BSDF_QUERY_SAMPLE = 0, MTSG_BSDF_QUERY_EVAL = 1 };
+enum { MTSG_BSDF_QUERY_OK = 1, MTSG_BSDF_QUERY_DELTA = 2, MTSG_BSDF_QUERY_NULL = 4 };
+int  mtsg_bsdf_query(mtsg_scene *scene, int32_t bsdf, int32_t mode, uint32_t n, const float *in, const float *alb, float *out,
+                     uint32_t *flags);
 
 /* Debug / parity entry: myPath2_OM's visibility query for n connections:
  * ids[i] = OccupancyMap::nearestOMindex(dirs[i]) (myOM.h:603-615) and

@@ -140,8 +140,11 @@ mtsh_builder *mtsh_scene_begin(const char *base_dir);
 /* `bitmap` texture (bitmap.cpp:179-302) -> texture id. */
 int32_t mtsh_scene_add_texture(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n_props);
 /* BSDF plugin (diffuse, roughconductor, conductor, dielectric,
- * roughdielectric, plastic, roughplastic, twosided) -> BSDF id.  nested:
- * twosided's one or two BSDF ids (twosided.cpp:52-80), else none. */
+ * roughdielectric, plastic, roughplastic, twosided, phong, ward,
+ * roughdiffuse, difftrans, thindielectric) -> BSDF id.  nested: twosided's
+ * one or two BSDF ids (twosided.cpp:52-80; not difftrans or
+ * thindielectric, which transmit), else none.  myPath2_OM scenes take the
+ * first eight alone. */
 int32_t mtsh_scene_add_bsdf(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n_props,
                             const int32_t *nested, int32_t n_nested);
 /* Emitter -> emitter id.  The six plugins and their properties (every one

@@ -63,7 +63,7 @@ DEV uint32_t block_append1(BlockAppend &ba, uint32_t *gcnt, bool p) {
 // radiance (ao: the value of a miss) and alpha to P.L, its refN to P.aux, and
 // the fan to D.F.
 // MATS: the material classes compiled in, as k_shade's (kernels.h MAT_*).
-template <int ENV, int SMP, bool EXT, int MATS = MATS_ALL>
+template <int ENV, int SMP, int EXT, int MATS = MATS_ALL>
 __global__ void __launch_bounds__(BLOCK) k_direct_shade(DevScene S, DevIntegrator I, DevBatch B, DevPaths P, DevDirect D, int hasAlpha) {
     __shared__ BlockAppend ba;
     const uint32_t slot = blockIdx.x * BLOCK + threadIdx.x;
@@ -223,7 +223,7 @@ __global__ void __launch_bounds__(BLOCK) k_direct_shade(DevScene S, DevIntegrato
                 stS(&F.ray_o[pos], make_float4(its.p.x, its.p.y, its.p.z, kEpsilon));
                 stS(&F.ray_d[pos], make_float4(wo.x, wo.y, wo.z, INFINITY));
                 stS(&D.val[pos], make_float4(bs.weight.x, bs.weight.y, bs.weight.z, bs.pdf));
-                D.flag[pos] = bs.delta ? 1u : 0u;
+                D.flag[pos] = EXT >= 2 ? bs.delta : (bs.delta ? 1u : 0u);
                 ++live;
             } else {   // no ray: the traversal skips it and writes no hit
                 stS(&F.ray_o[pos], make_float4(0.f, 0.f, 0.f, 0.f));
@@ -249,7 +249,8 @@ __global__ void __launch_bounds__(BLOCK) k_direct_shade(DevScene S, DevIntegrato
 // shadow rays' cells in index order, then the BSDF rays' emitter or
 // environment hits in index order (direct.cpp:276-305); ao: the mean of the
 // cells (ao.cpp:118-122).
-template <int ENV>
+// NULLEV: the scene's BSDFs can sample a null event (EXT level 2)
+template <int ENV, bool NULLEV = false>
 __global__ void __launch_bounds__(BLOCK) k_direct_resolve(DevScene S, DevIntegrator I, DevBatch B, DevPaths P, DevDirect D) {
     const uint32_t slot = blockIdx.x * BLOCK + threadIdx.x;
     if (slot >= B.nslots || camera_meta(B, slot).x == 0u) return;
@@ -277,9 +278,10 @@ __global__ void __launch_bounds__(BLOCK) k_direct_resolve(DevScene S, DevIntegra
             float3 value;
             float lumPdf = 0.0f;
             if (__float_as_uint(h.w) == 0xFFFFFFFFu) {
-                // the environment, if any (direct.cpp:285-294; no BSDF of this
-                // build has a null component, so hideEmitters hides nothing here)
+                // the environment, if any (direct.cpp:285-294): hideEmitters
+                // hides it from a null event (thindielectric's transmission)
                 if (!ENV) continue;
+                if (NULLEV && I.hide_emitters && (D.flag[pos] & 2u)) continue;
                 if (ENV == EM_ALL && !(S.has_env & 1)) {   // a constant environment, or none
                     const int ce = constant_emitter(S);
                     float pdfSA;
@@ -314,6 +316,7 @@ __global__ void __launch_bounds__(BLOCK) k_direct_resolve(DevScene S, DevIntegra
     stS(&P.L[slot], make_float4(L.x, L.y, L.z, L4.w));
 }
 
+#ifndef MTSG_TU_EXT2
 template <int SMP>
 void shade_smp(const DirectLaunch &a) {
     const dim3 g((a.B->nslots + BLOCK - 1) / BLOCK), b(BLOCK);
@@ -345,12 +348,37 @@ void shade_smp(const DirectLaunch &a) {
     else { if (ext) SHADE(false, true, MATS_ALL); else SHADE(false, false, MATS_ALL); }
 #undef SHADE
 }
+#endif
 
 }  // namespace
 
 namespace mtsg {
 
+#ifdef MTSG_TU_EXT2
+// the kernels of DirectLaunch::ext2 scenes (a BSDF type above roughplastic), in
+// a translation unit of their own: every emitter kind and every BSDF
+template <int SMP>
+static void shade_ext2(const DirectLaunch &a) {
+    const dim3 g((a.B->nslots + BLOCK - 1) / BLOCK), b(BLOCK);
+    hipLaunchKernelGGL((k_direct_shade<EM_ALL, SMP, 2, MATS_ALL>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D, a.hasAlpha);
+}
+void launch_direct_shade_ext2(const DirectLaunch &a) {
+    switch (a.I->smp.type) {
+        case MTSG_SAMPLER_HALTON: shade_ext2<MTSG_SAMPLER_HALTON>(a); break;
+        case MTSG_SAMPLER_HAMMERSLEY: shade_ext2<MTSG_SAMPLER_HAMMERSLEY>(a); break;
+        case MTSG_SAMPLER_LDSAMPLER: shade_ext2<MTSG_SAMPLER_LDSAMPLER>(a); break;
+        case MTSG_SAMPLER_SOBOL: shade_ext2<MTSG_SAMPLER_SOBOL>(a); break;
+        default: shade_ext2<MTSG_SAMPLER_INDEPENDENT>(a);
+    }
+}
+void launch_direct_resolve_ext2(const DirectLaunch &a) {
+    const dim3 g((a.B->nslots + BLOCK - 1) / BLOCK), b(BLOCK);
+    hipLaunchKernelGGL((k_direct_resolve<EM_ALL, true>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D);
+}
+#else
+
 void launch_direct_shade(const DirectLaunch &a) {
+    if (a.ext2 && !a.D->ao) { launch_direct_shade_ext2(a); return; }   // (ao reads no BSDF)
     switch (a.I->smp.type) {
         case MTSG_SAMPLER_HALTON: shade_smp<MTSG_SAMPLER_HALTON>(a); break;
         case MTSG_SAMPLER_HAMMERSLEY: shade_smp<MTSG_SAMPLER_HAMMERSLEY>(a); break;
@@ -362,9 +390,11 @@ void launch_direct_shade(const DirectLaunch &a) {
 
 void launch_direct_resolve(const DirectLaunch &a) {
     const dim3 g((a.B->nslots + BLOCK - 1) / BLOCK), b(BLOCK);
-    if (a.emx) hipLaunchKernelGGL((k_direct_resolve<EM_ALL>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D);
+    if (a.ext2 && !a.D->ao) launch_direct_resolve_ext2(a);
+    else if (a.emx) hipLaunchKernelGGL((k_direct_resolve<EM_ALL>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D);
     else if (a.env) hipLaunchKernelGGL((k_direct_resolve<true>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D);
     else hipLaunchKernelGGL((k_direct_resolve<false>), g, b, 0, a.stream, *a.S, *a.I, *a.B, *a.P, *a.D);
 }
+#endif   // MTSG_TU_EXT2
 
 }  // namespace mtsg

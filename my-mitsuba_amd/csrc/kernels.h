@@ -211,12 +211,19 @@ struct ShadeLaunch {
     bool env, ext, inst;   // inst: two-level instancing (k_finish<.., INST>)
     int mats;              // the scene's material classes (MAT_*), or MATS_ALL
     bool emx = false;      // the scene holds an emitter without a shape: the EM_ALL kernels (EXT, MATS_ALL)
+    bool ext2 = false;     // it holds a BSDF type above roughplastic: the EM_ALL kernels at EXT level 2 (emx is set too)
 };
 template <int SMP> void launch_shade_smp(const ShadeLaunch &a);
 template <int SMP> void launch_finish_smp(const ShadeLaunch &a);
+// the kernels of ShadeLaunch::ext2 scenes, in translation units of their own
+// (smp_kernels.hip compiled with MTSG_TU_EXT2): they build beside the others
+template <int SMP> void launch_shade_ext2(const ShadeLaunch &a);
+template <int SMP> void launch_finish_ext2(const ShadeLaunch &a);
 #define MTSG_DECLARE_LAUNCHERS(SMP) \
     template <> void launch_shade_smp<SMP>(const ShadeLaunch &a); \
-    template <> void launch_finish_smp<SMP>(const ShadeLaunch &a);
+    template <> void launch_finish_smp<SMP>(const ShadeLaunch &a); \
+    template <> void launch_shade_ext2<SMP>(const ShadeLaunch &a); \
+    template <> void launch_finish_ext2<SMP>(const ShadeLaunch &a);
 MTSG_DECLARE_LAUNCHERS(MTSG_SAMPLER_INDEPENDENT)
 MTSG_DECLARE_LAUNCHERS(MTSG_SAMPLER_HALTON)
 MTSG_DECLARE_LAUNCHERS(MTSG_SAMPLER_HAMMERSLEY)
@@ -284,7 +291,7 @@ struct DevDirect {
     DevPaths F;                      // ray_o / ray_d / hit / hitInst / tie: BSDF ray slot * nb + j;
                                      // sh_o / sh_d / sh_c: shadow rays, compacted; Lp: cell slot * ne + i
     float4 *val;                     // BSDF ray: bsdfVal, bsdfPdf
-    uint32_t *flag;                  // BSDF ray: 1 = sampled a delta component
+    uint32_t *flag;                  // BSDF ray: BsdfSample::delta (bit 0 a delta component, bit 1 the null event)
 };
 struct DirectLaunch {
     hipStream_t stream;
@@ -297,9 +304,12 @@ struct DirectLaunch {
     bool env, ext;   // as ShadeLaunch
     int mats;        // the scene's material classes (MAT_*), or MATS_ALL
     bool emx = false;   // as ShadeLaunch
+    bool ext2 = false;  // as ShadeLaunch
 };
 void launch_direct_shade(const DirectLaunch &a);     // after the camera rays' trace launch: the fan
 void launch_direct_resolve(const DirectLaunch &a);   // after the fan's trace launch: P.L
+void launch_direct_shade_ext2(const DirectLaunch &a);     // the same for DirectLaunch::ext2 scenes (direct.hip
+void launch_direct_resolve_ext2(const DirectLaunch &a);   // compiled with MTSG_TU_EXT2, a unit of its own)
 
 }  // namespace mtsg
 
@@ -2414,7 +2424,7 @@ __global__ void __launch_bounds__(BLOCK) k_camera_lens(DevCamera C, DevIntegrato
 struct BsdfSample {
     float3 wo, weight;
     float pdf, eta;
-    uint32_t delta;
+    uint32_t delta;   // bit 0: a delta event (BSDF::EDelta); bit 1: it is BSDF::ENull (EXT level 2 only)
 };
 
 // Material classes compiled into a shading kernel (MATS, a template parameter
@@ -2759,13 +2769,219 @@ DEV float rough_trans(const mtsg_bsdf &b, float cosTheta) {
     return fminf(1.0f, fmaxf(0.0f, r));
 }
 
+// ---- phong, ward, roughdiffuse, difftrans, thindielectric (EXT level 2) ----
+// Frame::sinTheta / cosPhi / sinPhi (frame.h:113-154)
+DEV float frame_sin_theta(float3 v) {
+    const float temp = 1.0f - v.z * v.z;
+    return temp <= 0.0f ? 0.0f : sqrtf(temp);
+}
+DEV float clamp_pm1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }   // math::clamp(v, -1, 1)
+DEV float safe_acos_m(float v) { return mt_acosf(fminf(1.0f, fmaxf(-1.0f, v))); }   // math.h safe_acos
+DEV float safe_sqrt_m(float v) { return sqrtf(fmaxf(0.0f, v)); }                    // math.h safe_sqrt
+
+// Phong::eval * cos and pdf (phong.cpp:122-181): b.alpha_u holds the exponent
+DEV float3 phong_eval(const mtsg_bsdf &b, float3 alb, float3 wi, float3 wo, float &pdf) {
+    pdf = 0.0f;
+    if (wi.z <= 0 || wo.z <= 0) return mk3(0, 0, 0);
+    const float alpha = dot(wo, mk3(-wi.x, -wi.y, wi.z)), exponent = b.alpha_u;
+    float3 result = mk3(0, 0, 0);
+    float specProb = 0.0f;
+    if (alpha > 0.0f) {
+        const float p = mt_powf(alpha, exponent);
+        result = ld3(b.spec_refl) * ((exponent + 2) * kInvTwoPi * p);
+        specProb = p * (exponent + 1.0f) / (2.0f * kPi);
+    }
+    result = result + alb * kInvPi;
+    pdf = b.spec_sampling_weight * specProb + (1 - b.spec_sampling_weight) * (kInvPi * wo.z);
+    return result * wo.z;
+}
+// Ward::eval * cos and pdf (ward.cpp:178-264): b.distribution holds the
+// variant.  std::pow(Float, int) is the double function (C++11), so the
+// factors that hold it are evaluated in double as the reference's are
+DEV float3 ward_eval(const mtsg_bsdf &b, float3 alb, float3 wi, float3 wo, float &pdf) {
+    pdf = 0.0f;
+    if (wi.z <= 0 || wo.z <= 0) return mk3(0, 0, 0);
+    const float alphaU = b.alpha_u, alphaV = b.alpha_v;
+    float3 result = mk3(0, 0, 0);
+    {
+        const float3 H = wi + wo;
+        float factor1;
+        if (b.distribution == MTSG_WARD_WARD) factor1 = 1.0f / (4.0f * kPi * alphaU * alphaV * sqrtf(wi.z * wo.z));
+        else if (b.distribution == MTSG_WARD_DUER) factor1 = 1.0f / (4.0f * kPi * alphaU * alphaV * wi.z * wo.z);
+        else factor1 = (float)((double)dot(H, H) / ((double)(kPi * alphaU * alphaV) * pow((double)H.z, 4.0)));
+        const float factor2 = H.x / alphaU, factor3 = H.y / alphaV;
+        const float exponent = -(factor2 * factor2 + factor3 * factor3) / (H.z * H.z);
+        const float specRef = factor1 * mt_fastexp(exponent);
+        if (specRef > 1e-10f) result = ld3(b.spec_refl) * specRef;
+    }
+    result = result + alb * kInvPi;
+    {
+        const float3 H = normalize(wi + wo);
+        const float factor1 = (float)(1.0 / ((double)(4.0f * kPi * alphaU * alphaV * dot(H, wi)) * pow((double)H.z, 3.0)));
+        const float factor2 = H.x / alphaU, factor3 = H.y / alphaV;
+        const float exponent = -(factor2 * factor2 + factor3 * factor3) / (H.z * H.z);
+        const float specProb = factor1 * mt_fastexp(exponent);
+        pdf = b.spec_sampling_weight * specProb + (1 - b.spec_sampling_weight) * (kInvPi * wo.z);
+    }
+    return result * wo.z;
+}
+// RoughDiffuse::eval * cos and pdf (roughdiffuse.cpp:128-227): b.alpha_u
+// holds alpha, b.nonlinear holds useFastApprox
+DEV float3 roughdiffuse_eval(const mtsg_bsdf &b, float3 alb, float3 wi, float3 wo, float &pdf) {
+    pdf = 0.0f;
+    if (wi.z <= 0 || wo.z <= 0) return mk3(0, 0, 0);
+    pdf = kInvPi * wo.z;
+    const float conversionFactor = 1 / sqrtf(2.0f);
+    const float sigma = b.alpha_u * conversionFactor;
+    const float sigma2 = sigma * sigma;
+    const float sinThetaI = frame_sin_theta(wi), sinThetaO = frame_sin_theta(wo);
+    float cosPhiDiff = 0;
+    if (sinThetaI > kEpsilon && sinThetaO > kEpsilon) {
+        const float sinPhiI = clamp_pm1(wi.y / sinThetaI), cosPhiI = clamp_pm1(wi.x / sinThetaI);
+        const float sinPhiO = clamp_pm1(wo.y / sinThetaO), cosPhiO = clamp_pm1(wo.x / sinThetaO);
+        cosPhiDiff = cosPhiI * cosPhiO + sinPhiI * sinPhiO;
+    }
+    if (b.nonlinear) {
+        const float A = 1.0f - 0.5f * sigma2 / (sigma2 + 0.33f), B = 0.45f * sigma2 / (sigma2 + 0.09f);
+        float sinAlpha, tanBeta;
+        if (wi.z > wo.z) { sinAlpha = sinThetaO; tanBeta = sinThetaI / wi.z; }
+        else { sinAlpha = sinThetaI; tanBeta = sinThetaO / wo.z; }
+        return alb * (kInvPi * wo.z * (A + B * fmaxf(cosPhiDiff, 0.0f) * sinAlpha * tanBeta));
+    }
+    const float thetaI = safe_acos_m(wi.z), thetaO = safe_acos_m(wo.z);
+    const float alpha = fmaxf(thetaI, thetaO), beta = fminf(thetaI, thetaO);
+    float sinAlpha, sinBeta, tanBeta;
+    if (wi.z > wo.z) { sinAlpha = sinThetaO; sinBeta = sinThetaI; tanBeta = sinThetaI / wi.z; }
+    else { sinAlpha = sinThetaI; sinBeta = sinThetaO; tanBeta = sinThetaO / wo.z; }
+    const float tmp = sigma2 / (sigma2 + 0.09f), tmp2 = (4 * kInvPi * kInvPi) * alpha * beta, tmp3 = 2 * beta * kInvPi;
+    const float C1 = 1.0f - 0.5f * sigma2 / (sigma2 + 0.33f);
+    float C2 = 0.45f * tmp;
+    const float C3 = 0.125f * tmp * tmp2 * tmp2, C4 = 0.17f * sigma2 / (sigma2 + 0.13f);
+    if (cosPhiDiff > 0) C2 *= sinAlpha;
+    else C2 *= sinAlpha - tmp3 * tmp3 * tmp3;
+    const float tanHalf = (sinAlpha + sinBeta) / (safe_sqrt_m(1.0f - sinAlpha * sinAlpha) + safe_sqrt_m(1.0f - sinBeta * sinBeta));
+    const float3 snglScat = alb * (C1 + cosPhiDiff * C2 * tanBeta + (1.0f - fabsf(cosPhiDiff)) * C3 * tanHalf);
+    const float3 dblScat = alb * alb * (C4 * (1.0f - cosPhiDiff * tmp3 * tmp3));
+    return (snglScat + dblScat) * (kInvPi * wo.z);
+}
+// ThinDielectric: R' = R + T^2 R / (1 - R^2) (thindielectric.cpp:209-213)
+DEV float thin_reflectance(const mtsg_bsdf &b, float3 wi) {
+    float R = fresnel_dielectric1(fabsf(wi.z), b.ior_eta);
+    const float T = 1 - R;
+    if (R < 1) R += T * T * R / (1 - R * R);
+    return R;
+}
+// eval * cos and pdf of the five models; false: b is none of them
+DEV bool bsdf_eval2(const mtsg_bsdf &b, float3 alb, float3 wi, float3 wo, float &pdf, float3 &val) {
+    val = mk3(0, 0, 0);
+    pdf = 0.0f;
+    if (b.type == MTSG_BSDF_PHONG) { val = phong_eval(b, alb, wi, wo, pdf); return true; }
+    if (b.type == MTSG_BSDF_WARD) { val = ward_eval(b, alb, wi, wo, pdf); return true; }
+    if (b.type == MTSG_BSDF_ROUGHDIFFUSE) { val = roughdiffuse_eval(b, alb, wi, wo, pdf); return true; }
+    if (b.type == MTSG_BSDF_DIFFTRANS) {   // difftrans.cpp:76-91
+        if (wi.z * wo.z >= 0) return true;
+        pdf = fabsf(wo.z) * kInvPi;
+        val = alb * (kInvPi * fabsf(wo.z));
+        return true;
+    }
+    return b.type == MTSG_BSDF_THINDIELECTRIC;   // delta components only
+}
+// sample(bRec, pdf, sample) of the five models; r.delta bit 1: the sampled
+// event is BSDF::ENull (it does not count as scattering, path.cpp:213)
+DEV bool bsdf_sample2(const mtsg_bsdf &b, float3 alb, float3 wi, float sx, float sy, BsdfSample &r, bool &ok) {
+    ok = false;
+    if (b.type == MTSG_BSDF_PHONG || b.type == MTSG_BSDF_WARD) {   // phong.cpp:183-240, ward.cpp:266-326
+        bool choseSpecular = true;
+        if (sx <= b.spec_sampling_weight) {
+            sx /= b.spec_sampling_weight;
+        } else {
+            sx = (sx - b.spec_sampling_weight) / (1 - b.spec_sampling_weight);
+            choseSpecular = false;
+        }
+        if (!choseSpecular) {
+            r.wo = cosine_hemisphere(sx, sy);
+        } else if (b.type == MTSG_BSDF_PHONG) {
+            const float3 R = mk3(-wi.x, -wi.y, wi.z);
+            const float exponent = b.alpha_u;
+            const float sinAlpha = sqrtf(1 - mt_powf(sy, 2 / (exponent + 1)));
+            const float cosAlpha = mt_powf(sy, 1 / (exponent + 1));
+            const float phi = (2.0f * kPi) * sx;
+            float sinPhi, cosPhi;
+            mt_sincosf(phi, &sinPhi, &cosPhi);
+            Frame3 f;
+            f.n = R;
+            coordinateSystem(R, f.s, f.t);
+            r.wo = f.toWorld(mk3(sinAlpha * cosPhi, sinAlpha * sinPhi, cosAlpha));
+            if (r.wo.z <= 0) return true;
+        } else {
+            const float alphaU = b.alpha_u, alphaV = b.alpha_v;
+            float phiH = mt_atanf(alphaV / alphaU * mt_tanf(2.0f * kPi * sy));
+            if (sy > 0.5f) phiH += kPi;
+            float sinPhiH, cosPhiH;
+            mt_sincosf(phiH, &sinPhiH, &cosPhiH);
+            const float sinPhiH2 = safe_sqrt_m(1.0f - cosPhiH * cosPhiH);
+            const float thetaH = mt_atanf(safe_sqrt_m(-mt_fastlog(sx) / ((cosPhiH * cosPhiH) / (alphaU * alphaU) +
+                                                                       (sinPhiH2 * sinPhiH2) / (alphaV * alphaV))));
+            float sinThetaH, cosThetaH;
+            mt_sincosf(thetaH, &sinThetaH, &cosThetaH);
+            const float3 H = mk3(sinThetaH * cosPhiH, sinThetaH * sinPhiH, cosThetaH);   // sphericalDirection
+            r.wo = H * (2.0f * dot(wi, H)) - wi;
+            if (r.wo.z <= 0.0f) return true;
+        }
+        float pdf;
+        const float3 val = b.type == MTSG_BSDF_PHONG ? phong_eval(b, alb, wi, r.wo, pdf) : ward_eval(b, alb, wi, r.wo, pdf);
+        if (pdf == 0) return true;
+        r.pdf = pdf;
+        r.weight = val / pdf;
+        ok = !isZero(r.weight);
+        return true;
+    }
+    if (b.type == MTSG_BSDF_ROUGHDIFFUSE) {   // roughdiffuse.cpp:241-251
+        if (wi.z <= 0) return true;
+        r.wo = cosine_hemisphere(sx, sy);
+        float pdf;
+        const float3 val = roughdiffuse_eval(b, alb, wi, r.wo, pdf);
+        r.pdf = kInvPi * r.wo.z;
+        r.weight = val / r.pdf;
+        ok = !isZero(r.weight);
+        return true;
+    }
+    if (b.type == MTSG_BSDF_DIFFTRANS) {   // difftrans.cpp:105-116
+        r.wo = cosine_hemisphere(sx, sy);
+        if (wi.z > 0) r.wo.z *= -1;
+        r.pdf = fabsf(r.wo.z) * kInvPi;
+        r.weight = alb;
+        ok = !isZero(r.weight);
+        return true;
+    }
+    if (b.type == MTSG_BSDF_THINDIELECTRIC) {   // thindielectric.cpp:203-232
+        const float R = thin_reflectance(b, wi);
+        if (sx <= R) {
+            r.delta = 1;
+            r.wo = mk3(-wi.x, -wi.y, wi.z);
+            r.pdf = R;
+            r.weight = ld3(b.spec_refl);
+        } else {
+            r.delta = 3;   // ENull, which EDelta includes
+            r.wo = -wi;
+            r.pdf = 1 - R;
+            r.weight = ld3(b.spec_trans);
+        }
+        ok = !isZero(r.weight);
+        return true;
+    }
+    return false;
+}
+
 // BSDF::eval * cos (ESolidAngle) and pdf for the smooth BSDFs.  EXT: the
 // scene has conductor / plastic / twosided records (the shade kernel is
 // instantiated without them otherwise: their code costs the common
-// diffuse + roughconductor + dielectric kernel its register budget)
+// diffuse + roughconductor + dielectric kernel its register budget); EXT
+// level 2: it holds one of the five models above, which only the kernels of
+// such scenes compile (k_shade / k_finish / k_direct_shade<EM_ALL, .., 2>)
 // alb: the record's reflectance (`reflectance` / `diffuseReflectance`), the
 // constant or its texture's value at the hit (texture_eval)
-template <bool EXT, int MATS = MATS_ALL>
+template <int EXT, int MATS = MATS_ALL>
 DEV float3 bsdf_eval1(const mtsg_bsdf &b, float3 alb, float3 wi, float3 wo, float &pdf) {
     pdf = 0.0f;
     if ((MATS & MAT_DIFFUSE) && b.type == MTSG_BSDF_DIFFUSE) {   // diffuse.cpp:107-126
@@ -2840,12 +3056,16 @@ DEV float3 bsdf_eval1(const mtsg_bsdf &b, float3 alb, float3 wi, float3 wo, floa
         pdf = mf.pdf(wi, H) * dwh_dwo * probSpecular + (1 - probSpecular) * (kInvPi * wo.z);
         return ld3(b.spec_refl) * value + plastic_diffuse(b, alb) * (kInvPi * wo.z * T12 * T21 * invEta2);
     }
+    if (EXT >= 2) {
+        float3 val;
+        if (bsdf_eval2(b, alb, wi, wo, pdf, val)) return val;
+    }
     return mk3(0, 0, 0);   // dielectric / conductor: delta components only
 }
 
 // next1d: the sampler's next1D, drawn only where Mitsuba draws it
 // (roughdielectric's reflect/refract choice: roughdielectric.cpp:531-539)
-template <bool EXT, int MATS, class Next1D>
+template <int EXT, int MATS, class Next1D>
 DEV bool bsdf_sample1(const mtsg_bsdf &b, float3 alb, float3 wi, float sx, float sy, BsdfSample &r, Next1D &&next1d) {
     r.eta = 1.0f;
     r.delta = 0;
@@ -2979,6 +3199,10 @@ DEV bool bsdf_sample1(const mtsg_bsdf &b, float3 alb, float3 wi, float sx, float
         }
         return !isZero(r.weight);
     }
+    if (EXT >= 2) {
+        bool ok;
+        if (bsdf_sample2(b, alb, wi, sx, sy, r, ok)) return ok;
+    }
     return false;
 }
 
@@ -2986,7 +3210,7 @@ DEV bool bsdf_sample1(const mtsg_bsdf &b, float3 alb, float3 wi, float sx, float
 // bsdfs[back] with the z components negated
 // alb belongs to the record that answers (the back record for back-side
 // queries of a twosided front record)
-template <bool EXT, int MATS = MATS_ALL>
+template <int EXT, int MATS = MATS_ALL>
 DEV float3 bsdf_eval(const mtsg_bsdf *all, const mtsg_bsdf &b, float3 alb, float3 wi, float3 wo, float &pdf) {
     if (EXT && b.twosided && !(wi.z > 0)) {
         wi.z = -wi.z;
@@ -2995,7 +3219,7 @@ DEV float3 bsdf_eval(const mtsg_bsdf *all, const mtsg_bsdf &b, float3 alb, float
     }
     return bsdf_eval1<EXT, MATS>(b, alb, wi, wo, pdf);
 }
-template <bool EXT, int MATS = MATS_ALL, class Next1D>
+template <int EXT, int MATS = MATS_ALL, class Next1D>
 DEV bool bsdf_sample(const mtsg_bsdf *all, const mtsg_bsdf &b, float3 alb, float3 wi, float sx, float sy, BsdfSample &r,
                      Next1D &&next1d) {
     if (EXT && b.twosided && wi.z < 0) {
@@ -3470,7 +3694,7 @@ DEV PathLoads load_path_rest(const DevScene &S, const DevPaths &P, uint32_t i, b
 #define MTSG_SHADE_PRELOAD 0   // measured r04: 1 (all) C3 -0.5%, C5 -3.5% (spills at the 128-VGPR cap); 2 (hit) C3 -0.4%
 #endif
 
-template <int ENV, int SMP, bool EXT, class Out, int MATS = MATS_ALL>
+template <int ENV, int SMP, int EXT, class Out, int MATS = MATS_ALL>
 DEV void shade_path(const DevScene &S, const DevIntegrator &I, const DevBatch &B, const DevPaths &P, bool first, uint32_t i,
                     const uint4 meta, const PathLoads &pl, int hasAlpha, Out &out, bool &cont, bool &shadow,
                     const ShadeTables &tb) {
@@ -3647,7 +3871,8 @@ DEV void shade_path(const DevScene &S, const DevIntegrator &I, const DevBatch &B
             if (!bsdf_sample<EXT, MATS>(S.bsdfs, bsdf, alb, wi, sx, sy, bs, [&]() { return next1D<SMP>(I, smp); })) {
                 done = true;
             } else {
-                flags |= F_SCATTERED;
+                // scattered |= bRec.sampledType != BSDF::ENull (path.cpp:213)
+                if (!(EXT >= 2 && (bs.delta & 2u))) flags |= F_SCATTERED;
                 const float3 wo = its.sh.toWorld(bs.wo);
                 if (I.strict_normals && dot(its.geoN, wo) * bs.wo.z <= 0) {
                     done = true;
@@ -4074,7 +4299,7 @@ DEV uint32_t shade_sort(uint32_t cls, uint32_t *cnt, uint16_t *perm) {
 // lookup of a primary miss, hideEmitters' camera case), 0 = later bounces only
 // (that code compiled out: C5's kernel then holds 96 VGPRs without spilling),
 // 2 = either (run-time)
-template <int ENV, int SMP, bool EXT, int MATS = MATS_ALL, int FIRST = 2>
+template <int ENV, int SMP, int EXT, int MATS = MATS_ALL, int FIRST = 2>
 __global__ void SHADE_ATTR(ENV, MATS) k_shade(DevScene S, DevIntegrator I, DevBatch B, DevPaths P, int bounce, int qin,
                                                  uint32_t nIdentity, int hasAlpha) {
     __shared__ BlockAppend ba;
@@ -4213,7 +4438,7 @@ inline bool finish_uses_mats(int smp, bool ext, bool inst, int mats) {
 // INST: the two-level traversal (and its exact tie retrace) is compiled only
 // into the instantiations for instanced scenes, so the flat kernel carries
 // neither its registers nor the retrace's scratch stack
-template <int ENV, int SMP, bool EXT, bool INST, int MATS = MATS_ALL>
+template <int ENV, int SMP, int EXT, bool INST, int MATS = MATS_ALL>
 __global__ void FINISH_ATTR(MATS) k_finish(DevScene S, DevIntegrator I, DevBatch B, DevPaths P, int qin, int hasAlpha, uint32_t shadeMin) {
     const SpecStack stk{};
     lds_top_init(S);

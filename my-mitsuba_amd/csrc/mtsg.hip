@@ -147,6 +147,7 @@ struct mtsg_scene {
     unsigned long long *waveTimes = nullptr;     // MTSG_FLAG_WAVETIME: [launch][wave][WT_WORDS]
     uint32_t wtLaunches = 0;
     bool extBsdfs = false;   // conductor / plastic / twosided records or textures present (k_shade<..., true>)
+    bool ext2 = false;       // a record of a type above roughplastic: the EM_ALL kernels at EXT level 2 (emitterSet is EM_ALL then)
     int mats = MATS_ALL;     // material classes of the scene's records (k_shade<..., MATS>)
     bool shadeGeneric = false;   // MTSG_OPT_SHADE_GENERIC: the all-materials kernel (A/B tests)
     // the scene's emitter kinds next to its material classes: EM_ALL with a
@@ -352,6 +353,7 @@ ShadeLaunch shade_args(mtsg_scene *s, const DevIntegrator &I, const DevBatch &B,
     a.ext = s->extBsdfs;
     a.inst = s->ds.inst != nullptr;
     a.emx = s->emitterSet == EM_ALL;
+    a.ext2 = s->ext2;
     a.mats = (s->shadeGeneric || a.emx) ? (int)MATS_ALL : s->mats;
     return a;
 }
@@ -632,7 +634,7 @@ struct RenderRun {
     }
     DirectLaunch direct_args(uint32_t l) const {
         return DirectLaunch{s->lstream[l], &s->ds, &I, &lane[l].B, &s->LP[l], &s->fan, s->cam.has_alpha, (s->ds.has_env & 1) != 0, s->extBsdfs,
-                            s->shadeGeneric ? (int)MATS_ALL : s->mats, s->emitterSet == EM_ALL};
+                            s->shadeGeneric ? (int)MATS_ALL : s->mats, s->emitterSet == EM_ALL, s->ext2};
     }
     FieldsLaunch fields(uint32_t l) const {
         return FieldsLaunch{s->lstream[l], &s->ds, &s->cam, &I, &lane[l].B, &s->LP[l], &s->aov, film, blockW, blockH, win};
@@ -1513,6 +1515,17 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
         if (b.type == MTSG_BSDF_CONDUCTOR || b.type == MTSG_BSDF_PLASTIC || b.type == MTSG_BSDF_ROUGHDIELECTRIC ||
             b.type == MTSG_BSDF_ROUGHPLASTIC || b.twosided)
             s->extBsdfs = true;
+        if (b.type > MTSG_BSDF_ROUGHPLASTIC && d->om) {
+            g_err = "myPath2_OM scenes take the BSDF types up to roughplastic only";
+            return fail(MTSG_ERR_INVALID);
+        }
+        // phong, ward, roughdiffuse, difftrans, thindielectric: only the
+        // all-kinds kernels at EXT level 2 hold them, so every other scene
+        // keeps the kernels it ran before
+        if (b.type > MTSG_BSDF_ROUGHPLASTIC) {
+            s->ext2 = s->extBsdfs = true;
+            s->emitterSet = EM_ALL;
+        }
         // the material classes the non-extended shading kernel must hold
         if (b.type == MTSG_BSDF_DIFFUSE) s->mats |= MAT_DIFFUSE;
         else if (b.type == MTSG_BSDF_ROUGHCONDUCTOR) s->mats |= b.distribution == MTSG_MF_GGX ? MAT_RC_GGX : MAT_RC_OTHER;
@@ -1777,7 +1790,7 @@ int mtsg_scene_kernel_sets(mtsg_scene *s, int32_t *material_set, int32_t *emitte
     if (!s || !material_set || !emitter_set) { g_err = "null argument"; return MTSG_ERR_INVALID; }
     // what shade_args hands the independent sampler's launchers
     const bool emx = s->emitterSet == EM_ALL;
-    *material_set = mats_kernel_set((s->shadeGeneric || emx) ? (int)MATS_ALL : s->mats) + ((s->extBsdfs || emx) ? 16 : 0);
+    *material_set = mats_kernel_set((s->shadeGeneric || emx) ? (int)MATS_ALL : s->mats) + ((s->extBsdfs || emx) ? 16 : 0) + (s->ext2 ? 32 : 0);
     *emitter_set = emx ? MTSG_EMITTER_SET_ALL : (s->ds.has_env & 1) ? MTSG_EMITTER_SET_ENVMAP : MTSG_EMITTER_SET_AREA;
     return MTSG_OK;
 }
@@ -2196,6 +2209,72 @@ int mtsg_om_query(mtsg_scene *s, uint32_t n, const float *dirs, const float *o1,
 }
 
 }  // extern "C"
+
+namespace {
+// mtsg_bsdf_query: bsdf_sample / bsdf_eval as the shading kernels call them,
+// at the widest EXT level, one thread per query; alb is the caller's, or the
+// constant of the record that answers: the back record of a twosided front
+// record where bsdf_eval (wi.z <= 0) or bsdf_sample (wi.z < 0) hands over to it
+__global__ void k_bsdf_query(DevScene S, int bsdf, int mode, uint32_t n, const float *in, const float *albIn, float *out,
+                             uint32_t *flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *q = in + 6 * (size_t)i;
+    const mtsg_bsdf &b = S.bsdfs[bsdf];
+    const float3 wi = mk3(q[0], q[1], q[2]);
+    const bool back = b.twosided && (mode == MTSG_BSDF_QUERY_EVAL ? !(wi.z > 0) : wi.z < 0);
+    const mtsg_bsdf &eff = back ? S.bsdfs[b.back] : b;
+    const float3 alb = albIn ? ld3(albIn + 3 * (size_t)i) : ld3(eff.reflectance);
+    if (mode == MTSG_BSDF_QUERY_EVAL) {
+        float pdf;
+        const float3 v = bsdf_eval<2>(S.bsdfs, b, alb, wi, mk3(q[3], q[4], q[5]), pdf);
+        float *o = out + 4 * (size_t)i;
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = pdf;
+        if (flags) flags[i] = MTSG_BSDF_QUERY_OK;
+        return;
+    }
+    BsdfSample r;
+    r.wo = r.weight = mk3(0, 0, 0);
+    r.pdf = 0.0f;
+    const float u = q[5];
+    const bool ok = bsdf_sample<2>(S.bsdfs, b, alb, wi, q[3], q[4], r, [&]() { return u; });
+    float *o = out + 8 * (size_t)i;
+    if (ok) {
+        o[0] = r.wo.x; o[1] = r.wo.y; o[2] = r.wo.z;
+        o[3] = r.weight.x; o[4] = r.weight.y; o[5] = r.weight.z;
+        o[6] = r.pdf; o[7] = r.eta;
+        flags[i] = MTSG_BSDF_QUERY_OK | ((r.delta & 1u) ? MTSG_BSDF_QUERY_DELTA : 0u) | ((r.delta & 2u) ? MTSG_BSDF_QUERY_NULL : 0u);
+    } else {
+        for (int k = 0; k < 8; ++k) o[k] = 0.0f;
+        flags[i] = 0u;
+    }
+}
+}  // namespace
+
+extern "C" int mtsg_bsdf_query(mtsg_scene *s, int32_t bsdf, int32_t mode, uint32_t n, const float *in, const float *alb, float *out,
+                               uint32_t *flags) {
+    if (!s || (n && (!in || !out)) || (mode != MTSG_BSDF_QUERY_SAMPLE && mode != MTSG_BSDF_QUERY_EVAL) ||
+        (mode == MTSG_BSDF_QUERY_SAMPLE && n && !flags)) {
+        g_err = "invalid arguments";
+        return MTSG_ERR_INVALID;
+    }
+    if (bsdf < 0 || (uint32_t)bsdf >= s->ds.n_bsdfs) { g_err = "BSDF index out of range"; return MTSG_ERR_INVALID; }
+    if (n == 0) return MTSG_OK;
+    int rc;
+    if ((rc = set_device(s)) != MTSG_OK) return rc;
+    const size_t no = mode == MTSG_BSDF_QUERY_EVAL ? 4 : 8;
+    hipError_t e = hipSuccess;
+    DevBuf<float> din(e, (size_t)n * 6, in), dalb(e, alb ? (size_t)n * 3 : 0, alb), dout(e, (size_t)n * no);
+    DevBuf<uint32_t> df(e, flags ? n : 0);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_bsdf_query, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, (int)bsdf, (int)mode, n, din.p, dalb.p, dout.p, df.p);
+        e = hipStreamSynchronize(s->stream);
+    }
+    dout.download(out);
+    if (flags) df.download(flags);
+    if (e != hipSuccess) { g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
+    return MTSG_OK;
+}
 
 namespace mtsg {
 void set_last_error(const std::string &e) { g_err = e; }   // kdbuild.hip

@@ -11,6 +11,20 @@
 
 namespace mtsg {
 
+#ifdef MTSG_TU_EXT2
+// this sampler's kernels for scenes with a phong, ward, roughdiffuse, difftrans
+// or thindielectric record: every emitter kind and every BSDF (EXT level 2)
+template <>
+void launch_shade_ext2<MTSG_TU_SAMPLER>(const ShadeLaunch &a) {
+    hipLaunchKernelGGL((k_shade<EM_ALL, MTSG_TU_SAMPLER, 2>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
+}
+template <>
+void launch_finish_ext2<MTSG_TU_SAMPLER>(const ShadeLaunch &a) {
+    if (a.inst) hipLaunchKernelGGL((k_finish<EM_ALL, MTSG_TU_SAMPLER, 2, true>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.qin, a.hasAlpha, a.shadeMin);
+    else hipLaunchKernelGGL((k_finish<EM_ALL, MTSG_TU_SAMPLER, 2, false>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.qin, a.hasAlpha, a.shadeMin);
+}
+#else
+
 // the material-specialised kernels (MATS), one for bounce 0 and one for the
 // later bounces (FIRST); the generic kernel decides at run time
 template <int SMP, int MATS>
@@ -39,6 +53,10 @@ void launch_shade_smp<MTSG_TU_SAMPLER>(const ShadeLaunch &a) {
 #endif
     // a scene with a point, spot, directional or constant emitter: the one
     // kernel that holds every emitter kind (and every BSDF: EXT, MATS_ALL)
+    if (a.ext2) {   // a phong, ward, roughdiffuse, difftrans or thindielectric record: the same kernel with them
+        launch_shade_ext2<SMP>(a);
+        return;
+    }
     if (a.emx) {
         hipLaunchKernelGGL((k_shade<EM_ALL, SMP, true>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
         return;
@@ -72,7 +90,7 @@ void launch_finish_mats(const ShadeLaunch &a) {
 }
 template <int SMP, bool INST>
 void launch_finish_inst(const ShadeLaunch &a) {
-    if (a.emx) {   // as launch_shade_smp
+    if (a.emx) {
         hipLaunchKernelGGL((k_finish<EM_ALL, SMP, true, INST>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.qin, a.hasAlpha, a.shadeMin);
         return;
     }
@@ -96,7 +114,8 @@ void launch_finish_inst(const ShadeLaunch &a) {
 
 template <>
 void launch_finish_smp<MTSG_TU_SAMPLER>(const ShadeLaunch &a) {
-    if (a.inst) launch_finish_inst<MTSG_TU_SAMPLER, true>(a);
+    if (a.ext2) launch_finish_ext2<MTSG_TU_SAMPLER>(a);   // as launch_shade_smp
+    else if (a.inst) launch_finish_inst<MTSG_TU_SAMPLER, true>(a);
     else launch_finish_inst<MTSG_TU_SAMPLER, false>(a);
 }
 
@@ -118,5 +137,6 @@ int finish_blocks_per_cu(bool mats) {
     return std::min(perCU, perCU2);
 }
 #endif
+#endif   // MTSG_TU_EXT2
 
 }  // namespace mtsg

@@ -284,6 +284,13 @@ void Scene::finalize() {
     // ---------------- BSDFs ----------------
     bsdfDesc.clear();
     for (auto &b : bsdfs) bsdfDesc.push_back(b.d);
+    if (integrator.type == "myPath2_OM")
+        for (auto &b : bsdfs)
+            if (b.d.type > MTSG_BSDF_ROUGHPLASTIC) {
+                static const char *names[] = {"phong", "ward", "roughdiffuse", "difftrans", "thindielectric"};
+                throw std::runtime_error(std::string("myPath2_OM: the ") + names[b.d.type - MTSG_BSDF_PHONG] +
+                                         " BSDF is outside this build's scope (its shading kernel holds the earlier plugins only)");
+            }
 
     // ---------------- emitters ----------------
     emitterDesc.clear(); emitterCdf.clear(); emitterTriCdf.clear();

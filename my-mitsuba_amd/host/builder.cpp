@@ -349,6 +349,40 @@ V3 SceneBuilder::reflectance(const Properties &props, int tex, const V3 &constan
     return V3(tt.average[0], tt.average[1], tt.average[2]) * tt.scale;
 }
 
+// The pair form of ensureEnergyConservation (bsdf.cpp:115-146) for phong and
+// ward: when the component-wise maximum of specular + diffuse exceeds 1, both
+// are scaled by 0.99 / max (the diffuse texture through its `scale`).
+// Returns the diffuse value used for getAverage() and sets d.texture
+V3 SceneBuilder::reflectancePair(const Properties &props, int tex, const V3 &diffuse, V3 &specular, mtsg_bsdf &d) {
+    V3 dmax = diffuse;
+    if (tex >= 0) {
+        const mtsg_texture &t = scene.textures[tex].d;
+        dmax = V3(t.maximum[0], t.maximum[1], t.maximum[2]) * t.scale;
+    }
+    const V3 sum = specular + dmax;
+    const float actualMax = std::max(sum.x, std::max(sum.y, sum.z));
+    float scale = 1.0f;
+    const bool rescale = props.getBool("ensureEnergyConservation", true) && actualMax > 1.0f;
+    if (rescale) {
+        scale = 0.99f * (1.0f / actualMax);
+        specular = specular * scale;
+    }
+    if (tex < 0) {
+        d.texture = 0;
+        return rescale ? diffuse * scale : diffuse;
+    }
+    if (rescale) {   // as reflectance(): the BSDF's own scaled copy
+        Texture copy = scene.textures[tex];
+        copy.id.clear();
+        copy.d.scale = copy.d.scale * scale;
+        scene.textures.push_back(copy);
+        tex = (int)scene.textures.size() - 1;
+    }
+    const mtsg_texture &tt = scene.textures[tex].d;
+    d.texture = tex + 1;
+    return V3(tt.average[0], tt.average[1], tt.average[2]) * tt.scale;
+}
+
 int SceneBuilder::bsdf(const std::string &type_, const Properties &props, const std::map<std::string, int> &textures,
                        const std::vector<int> &nested, const std::string &id, int line) {
     const std::string type = lower(type_);
@@ -470,6 +504,69 @@ int SceneBuilder::bsdf(const std::string &type_, const Properties &props, const 
         d.fdr_int = 1 - roughDiffuseTransmittance(d.distribution, d.alpha_u, d.ior_inv_eta);
         d.smooth = 1;        // glossy + diffuse components
         d.ref_n_zero = 0;
+    } else if (type == "phong" || type == "ward") {
+        // phong.cpp:60-107, ward.cpp:97-171: a glossy lobe over a diffuse base
+        const int tex = texturedParam(textures, {"diffuseReflectance"}, type, line, nTex);
+        if (type == "ward") {
+            const std::string variant = lower(props.getString("variant", "balanced"));
+            if (variant == "ward") d.distribution = MTSG_WARD_WARD;
+            else if (variant == "ward-duer") d.distribution = MTSG_WARD_DUER;
+            else if (variant == "balanced") d.distribution = MTSG_WARD_BALANCED;
+            else throw err(at(line) + "ward: Specified an invalid model type \"" + variant +
+                           "\", must be \"ward\", \"ward-duer\", or \"balanced\"!");
+            const float alpha = props.getFloat("alpha", 0.1f);
+            d.alpha_u = props.getFloat("alphaU", alpha);
+            d.alpha_v = props.getFloat("alphaV", alpha);
+            d.type = MTSG_BSDF_WARD;
+        } else {
+            d.alpha_u = props.getFloat("exponent", 30.0f);
+            d.type = MTSG_BSDF_PHONG;
+        }
+        V3 sr = props.getSpectrum("specularReflectance", V3(0.2f));
+        const V3 dr = reflectancePair(props, tex, props.getSpectrum("diffuseReflectance", V3(0.5f)), sr, d);
+        const float dAvg = luminance(dr), sAvg = luminance(sr);
+        d.spec_sampling_weight = sAvg / (dAvg + sAvg);
+        for (int i = 0; i < 3; ++i) { d.spec_refl[i] = sr[i]; d.reflectance[i] = dr[i]; }
+        d.smooth = 1;        // EGlossyReflection | EDiffuseReflection, EFrontSide
+        d.ref_n_zero = 0;
+    } else if (type == "roughdiffuse") {
+        // roughdiffuse.cpp:88-122: Oren-Nayar, one EGlossyReflection | EFrontSide component
+        float mx;
+        const int tex = texturedParam(textures, {"reflectance", "diffuseReflectance"}, type, line, nTex);
+        const V3 r = reflectance(props, tex,
+                                 props.getSpectrum(props.has("reflectance") ? "reflectance" : "diffuseReflectance", V3(0.5f)), d, mx);
+        d.type = MTSG_BSDF_ROUGHDIFFUSE;
+        d.nonlinear = props.getBool("useFastApprox", false) ? 1 : 0;
+        d.alpha_u = props.getFloat("alpha", 0.2f);
+        for (int i = 0; i < 3; ++i) d.reflectance[i] = r[i];
+        d.smooth = 1;
+        d.ref_n_zero = 0;
+    } else if (type == "difftrans") {
+        // difftrans.cpp:49-74: EDiffuseTransmission | EFrontSide | EBackSide
+        float mx;
+        const int tex = texturedParam(textures, {"transmittance", "diffuseTransmittance"}, type, line, nTex);
+        const V3 t = reflectance(props, tex,
+                                 props.getSpectrum(props.has("transmittance") ? "transmittance" : "diffuseTransmittance", V3(0.5f)), d, mx);
+        d.type = MTSG_BSDF_DIFFTRANS;
+        for (int i = 0; i < 3; ++i) d.reflectance[i] = t[i];
+        d.smooth = 1;
+        d.ref_n_zero = 1;    // ETransmission | EBackSide
+    } else if (type == "thindielectric") {
+        // thindielectric.cpp:73-128: EDeltaReflection and ENull, both sides
+        texturedParam(textures, {}, type, line, nTex);
+        float intIOR = lookupIORProp(props, "intIOR", "bk7");
+        float extIOR = lookupIORProp(props, "extIOR", "air");
+        if (intIOR < 0 || extIOR < 0) throw err("thindielectric: The interior and exterior indices of refraction must be positive!");
+        // (equal indices: a pane that does nothing; rejected like the rough models' case)
+        if (intIOR == extIOR) throw err(at(line) + "thindielectric: the interior and exterior indices of refraction must differ");
+        V3 sr = energyConserving(props, props.getSpectrum("specularReflectance", V3(1.0f)));
+        V3 st = energyConserving(props, props.getSpectrum("specularTransmittance", V3(1.0f)));
+        d.type = MTSG_BSDF_THINDIELECTRIC;
+        d.ior_eta = intIOR / extIOR;
+        d.ior_inv_eta = 1 / d.ior_eta;
+        for (int i = 0; i < 3; ++i) { d.spec_refl[i] = sr[i]; d.spec_trans[i] = st[i]; }
+        d.smooth = 0;        // delta components only
+        d.ref_n_zero = 1;    // EBackSide
     } else if (type == "twosided") {
         // twosided.cpp:52-80: one or two nested BRDFs, front and back
         texturedParam(textures, {}, type, line, nTex);
@@ -480,6 +577,9 @@ int SceneBuilder::bsdf(const std::string &type_, const Properties &props, const 
             const mtsg_bsdf &kd = scene.bsdfs[k].d;
             if (kd.type == MTSG_BSDF_DIELECTRIC || kd.type == MTSG_BSDF_ROUGHDIELECTRIC)
                 throw err("Only materials without a transmission component can be nested!");
+            if (kd.type == MTSG_BSDF_DIFFTRANS || kd.type == MTSG_BSDF_THINDIELECTRIC)
+                throw err(at(line) + "twosided: Only materials without a transmission component can be nested! (the nested BSDF is a " +
+                          std::string(kd.type == MTSG_BSDF_DIFFTRANS ? "difftrans" : "thindielectric") + ")");
             if (kd.twosided) throw err("twosided: a nested twosided material is not supported by this build");
         }
         const int backIdx = nested.size() == 2 ? nested[1] : nested[0];
@@ -1205,6 +1305,9 @@ void Scene::buildAov() {
         float scale = 0.0f;
         bool diffuse = true;
         if (b.type == MTSG_BSDF_DIFFUSE) scale = 1.0f;   // diffuse.cpp:106-108
+        // phong.cpp:109-111, ward.cpp:173-175, roughdiffuse.cpp:124-126: the parameter
+        // (difftrans, thindielectric: the base class's default, zero)
+        else if (b.type == MTSG_BSDF_PHONG || b.type == MTSG_BSDF_WARD || b.type == MTSG_BSDF_ROUGHDIFFUSE) scale = 1.0f;
         else if (b.type == MTSG_BSDF_PLASTIC) scale = 1 - fresnelDiffuseReflectance(b.ior_eta);   // plastic.cpp:195,219-221
         else if (b.type == MTSG_BSDF_ROUGHPLASTIC)   // roughplastic.cpp:309-320: Ftr = external evalDiffuse(alpha)
             scale = roughDiffuseTransmittance(b.distribution, b.alpha_u, b.ior_eta);

@@ -351,6 +351,7 @@ private:
     IntegratorProps pendingPath;   // the `path` child's own properties
     bool havePendingPath = false;
     V3 reflectance(const Properties &props, int tex, const V3 &constant, mtsg_bsdf &d, float &maxOut);
+    V3 reflectancePair(const Properties &props, int tex, const V3 &diffuse, V3 &specular, mtsg_bsdf &d);
     int defaultBsdf(bool emitter);
     void checkEmitter(int emitter, bool inGroup, bool claim);
     ShapeGroup &groupAt(int group);

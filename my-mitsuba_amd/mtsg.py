@@ -313,7 +313,7 @@ DEVICE_SYMBOLS = [
     "mtsg_sampler_draws", "mtsg_camera_rays", "mtsg_debug_wavetimes", "mtsg_set_tile_callback",
     "mtsg_debug_stragglers", "mtsg_set_test_knobs", "mtsg_set_option",
     "mtsg_scene_set_aov", "mtsg_render_multi", "mtsg_render_device_multi", "mtsg_render_device_tiles_multi",
-    "mtsg_render_samples_multi", "mtsg_scene_set_direct", "mtsg_scene_kernel_sets",
+    "mtsg_render_samples_multi", "mtsg_scene_set_direct", "mtsg_scene_kernel_sets", "mtsg_bsdf_query",
 ]
 HOST_SYMBOLS = [
     "mtsh_scene_load", "mtsh_scene_load_overrides", "mtsh_scene_load_props", "mtsh_scene_set_scene_props", "mtsh_set_kd_threads", "mtsh_set_instancing", "mtsh_scene_desc", "mtsh_scene_render_params",
@@ -477,6 +477,8 @@ def device_lib() -> C.CDLL:
         lib.mtsg_set_option.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
         if hasattr(lib, "mtsg_scene_kernel_sets"):   # (an MTSG_LIB build from before the query; GPUScene.kernel_sets then raises)
             lib.mtsg_scene_kernel_sets.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        if hasattr(lib, "mtsg_bsdf_query"):   # (as above; GPUScene.bsdf_query then raises)
+            lib.mtsg_bsdf_query.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mtsg_trace_closest.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mtsg_trace_shadow.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1093,6 +1095,35 @@ class GPUScene:
             pd = _ptr(duv)
         self._check(device_lib().mtsg_tex_eval(self._h, tex, uv.shape[0], _ptr(uv), pd, _ptr(out)), "mtsg_tex_eval")
         return out
+
+    def bsdf_query(self, bsdf: int, wi: np.ndarray, sample: np.ndarray | None = None, wo: np.ndarray | None = None,
+                   alb: np.ndarray | None = None):
+        """BSDF::sample / eval / pdf of BSDF record `bsdf` (debug entry point),
+        through the functions the shading kernels call.  With `sample` (n, 3) =
+        (sample.x, sample.y, the next1D value): returns (wo (n, 3), weight
+        (n, 3), pdf, eta, flags), flags holding BSDF_QUERY_OK / _DELTA / _NULL.
+        With `wo` (n, 3): returns (eval * cos (n, 3), pdf).  alb (n, 3): the
+        textured parameter's value per query (default: the record's constant)."""
+        if (sample is None) == (wo is None):
+            raise ValueError("bsdf_query takes either `sample` or `wo`")
+        wi = np.ascontiguousarray(wi, dtype=np.float32).reshape(-1, 3)
+        other = np.ascontiguousarray(sample if wo is None else wo, dtype=np.float32).reshape(-1, 3)
+        if other.shape != wi.shape:
+            raise ValueError("bsdf_query: one row of `sample` / `wo` per row of `wi`")
+        n = wi.shape[0]
+        q = np.ascontiguousarray(np.concatenate([wi, other], axis=1))
+        flags = np.zeros(n, np.uint32)
+        pa = None
+        if alb is not None:
+            alb = np.ascontiguousarray(np.broadcast_to(np.asarray(alb, np.float32), (n, 3)))
+            pa = _ptr(alb)
+        if wo is None:
+            out = np.zeros((n, 8), np.float32)
+            self._check(device_lib().mtsg_bsdf_query(self._h, bsdf, 0, n, _ptr(q), pa, _ptr(out), _ptr(flags)), "mtsg_bsdf_query")
+            return out[:, 0:3].copy(), out[:, 3:6].copy(), out[:, 6].copy(), out[:, 7].copy(), flags
+        out = np.zeros((n, 4), np.float32)
+        self._check(device_lib().mtsg_bsdf_query(self._h, bsdf, 1, n, _ptr(q), pa, _ptr(out), _ptr(flags)), "mtsg_bsdf_query")
+        return out[:, 0:3].copy(), out[:, 3].copy()
 
     def om_query(self, dirs: np.ndarray, o1: np.ndarray, o2: np.ndarray):
         """myPath2_OM visibility (debug entry point): (map ids, visible flags)."""
