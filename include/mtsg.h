@@ -677,7 +677,7 @@ int  mtsg_debug_wavetimes(mtsg_scene *scene, uint64_t *out, uint32_t max_launche
 int  mtsg_debug_stragglers(mtsg_scene *scene, float *out, uint32_t max_rays);
 
 /* Wavefront batch size in paths.  Default: the whole rectangle, up to
- * 3 * 2^28 paths (280 B of path state each) and at most 3/4 of the free
+ * 3 * 2^28 paths (276 B of path state each) and at most 3/4 of the free
  * device memory; larger renders run in equal batches. */
 int  mtsg_set_batch_paths(mtsg_scene *scene, uint32_t paths);
 
@@ -714,6 +714,14 @@ int  mtsg_set_finish_paths(mtsg_scene *scene, uint32_t paths);
  *                             scene's rectangles once per ray at its setup, where
  *                             the scene has few enough of them, 0 = in the kd-tree
  *                             leaves, as every other traversal does (A/B tests)
+ *   MTSG_OPT_RAY_PRESETUP     flat scenes in that mode, `path` renders and ray
+ *                             queries: 0 (default) = the traversal tests the
+ *                             rectangles as it takes a ray up, 1 = the kernels
+ *                             that make the rays test them and leave each ray's
+ *                             result for the traversal (a shadow ray that a
+ *                             rectangle occludes is not sent to it, so
+ *                             mtsg_stats::rays_shadow counts the rays traced;
+ *                             measured slower)
  * Unknown keys and values out of range return MTSG_ERR_INVALID. */
 /* the most rectangles a flat scene may hold for MTSG_OPT_RECT_SETUP 1 to apply */
 #define MTSG_RECT_SETUP_CAP 2u
@@ -725,7 +733,8 @@ enum {
     MTSG_OPT_SHADE_GENERIC = 5,
     MTSG_OPT_RAY_ORDER = 6,
     MTSG_OPT_CAMERA_DIFFS = 7,
-    MTSG_OPT_RECT_SETUP = 8
+    MTSG_OPT_RECT_SETUP = 8,
+    MTSG_OPT_RAY_PRESETUP = 9
 };
 int  mtsg_set_option(mtsg_scene *scene, int32_t key, int64_t value);
 

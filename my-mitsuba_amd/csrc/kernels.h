@@ -188,7 +188,17 @@ struct DevPaths {
     // closest rays of a trace launch in ray order (k_sortwin): work-list entry
     // i is the ray at position order[i]; nullptr: entry i is position i
     uint32_t *order;
-    uint32_t *orderBuf;   // the buffer k_sortwin fills (one entry per path)
+    uint32_t *orderBuf;   // the buffer k_sortwin fills (one entry per path; allocated with MTSG_OPT_RAY_ORDER 1 only)
+    // Flat scenes in the setup mode: the rectangle pre-record of closest ray i
+    // (ray_prerecord: t, u, v, 0x80000000 | PRE_TIE | rectangle, or the miss
+    // record), written by the kernel that makes the ray (k_camera, k_shade) and
+    // read by the trace launch's refill in place of its own rectangle loop;
+    // nullptr: the launch's rays carry none.  One array serves every bounce:
+    // the trace launch of bounce b + 1 has read entry i before the shade
+    // launch of bounce b + 1 writes it (the launches of a batch are ordered on
+    // its lane's stream, and every lane has its own DevPaths).
+    float4 *pre = nullptr;
+    float4 *preBuf = nullptr;   // the array itself (one entry per path; allocated with MTSG_OPT_RAY_PRESETUP 1 only)
     // 1 while the closest rays are bounce 0's camera rays of a flat scene,
     // which k_camera stores as ray_d = (direction, 1/z) only: their origin is
     // the camera's and mint / maxt are near / far clip x 1/z (load_closest_ray,
@@ -242,6 +252,10 @@ struct FlatTraceLaunch {
     unsigned long long *wt;
     bool count, knobs, refill32, tie;
     bool rectSetup;   // the setup-mode kernels (rectangles tested at ray setup); false: k_trace_s_leaf
+    // the launch's rays carry pre-records (P->pre; the closest rays' producer
+    // wrote them and dropped the shadow rays a rectangle occludes): the refill
+    // runs no rectangle loop (k_trace_s_pre).  Only with rectSetup and without knobs.
+    bool pre = false;
 };
 void launch_trace_flat(const FlatTraceLaunch &a);
 int trace_flat_blocks_per_cu();   // k_trace_s<false, 16> workgroups per CU (occupancy query)
@@ -431,7 +445,10 @@ constexpr uint32_t DEFAULT_BATCH_PATHS = 3u << 28;
 #ifndef MTSG_LANES
 #define MTSG_LANES 1
 #endif
-constexpr size_t PATH_STATE_BYTES = 280;    // bytes per path slot (DevPaths: 2 x 96 dense + hit, L, 3 x shadow, tie, order)
+// bytes per path slot (DevPaths: 2 x 96 dense + hit, L, 3 x shadow, tie); the order
+// buffer's and the pre-records' bytes more once MTSG_OPT_RAY_ORDER 1 /
+// MTSG_OPT_RAY_PRESETUP 1 ask for them (ensure_batch)
+constexpr size_t PATH_STATE_BYTES = 276, PATH_ORDER_BYTES = 4, PATH_PRE_BYTES = 16;
 #ifndef MTSG_SHORT_STACK
 #define MTSG_SHORT_STACK 6   // 6 x 12 B x 64 lanes = 4.6 KB LDS/wave -> 8 waves/SIMD (8: 6.5, 12: 4.2)
 #endif
@@ -810,8 +827,19 @@ DEV uint32_t lane_here() {
 DEV uint32_t rank_below(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
+// MTSG_STACK_LANE=1 (set by trace_flat.hip for the flat kernels): the stack
+// keeps the lane's index in a VGPR, filled once per kernel, instead of
+// recomputing it at every use (profiles/ray_presetup_ab.txt)
+#ifndef MTSG_STACK_LANE
+#define MTSG_STACK_LANE 0
+#endif
 struct SpecStack {
+#if MTSG_STACK_LANE
+    uint32_t lane = threadIdx.x;   // (one wave per workgroup)
+    DEV uint32_t at(uint32_t k) const { return k * TRACE_BLOCK + lane; }
+#else
     DEV static uint32_t at(uint32_t k) { return k * TRACE_BLOCK + lane_here(); }
+#endif
     DEV void push(uint32_t k, uint2 node, float t) const {
         const uint32_t i = at(k);
         s_specNode[i] = node;
@@ -854,20 +882,18 @@ DEV float4 miss_record() {
 // A closest ray's best rectangle is written to hitOut; a shadow ray that hits
 // a rectangle is occluded: false with SB_FOUND in r.bits (false otherwise
 // leaves r.bits 0), the caller does nothing more for it.
-template <bool RS = false>
-DEV bool spec_init(const DevScene &S, float3 o, float3 d, float rayMint, float rayMaxt, bool shadow, SpecRay &r,
-                   float4 *hitOut = nullptr) {
-    if (RS) r.bits = 0u;
-    r.o = o;
-    r.d = d;
-    r.inv = mk3(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
-    const uint32_t dneg = (d.x <= 0.0f ? 1u : 0u) | (d.y <= 0.0f ? 2u : 0u) | (d.z <= 0.0f ? 4u : 0u);
+// RS_PRE: the loop ran where the ray was made, at full wave width, and the
+// refill reads its 16-B result (ray_prerecord below).
+
+// the ray's interval: false when it misses the scene bounds or the interval is empty
+DEV bool ray_interval(const DevScene &S, float3 o, float3 d, float3 inv, float rayMint, float rayMaxt, bool shadow, float &mint,
+                      float &best) {
     float nearT = -INFINITY, farT = INFINITY;
     bool ok = true;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         // the two cases of aabb.h:308-338 as selects (no exec-mask branches)
-        const float oi = comp(o, i), di = comp(d, i), ii = comp(r.inv, i);
+        const float oi = comp(o, i), di = comp(d, i), ii = comp(inv, i);
         const bool par = di == 0.0f;
         const float t1 = (S.bmin[i] - oi) * ii, t2 = (S.bmax[i] - oi) * ii;
         nearT = par ? nearT : fmaxf(fminf(t1, t2), nearT);
@@ -879,9 +905,72 @@ DEV bool spec_init(const DevScene &S, float3 o, float3 d, float rayMint, float r
     float m = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
     if (!shadow) m = fmaxf(m, kEpsilon);
     const float rayMinT = rayMint == kEpsilon ? rayMint * m : rayMint;
-    r.mint = fmaxf(nearT, rayMinT);
-    r.best = fminf(farT, rayMaxt);
-    if (!(r.best > r.mint)) return false;
+    mint = fmaxf(nearT, rayMinT);
+    best = fminf(farT, rayMaxt);
+    return best > mint;
+}
+
+// The rectangles of a setup-mode scene against a ray on its interval
+// [mint, best]: the loop of "rectangles at setup".  Returns the hit record of
+// the ray's best rectangle (t, u, v, 0x80000000 | k) or the miss record, and in
+// `tie` whether a test met the exact-tie condition of spec_iter (a hit at the
+// best distance so far under another key).  A shadow ray keeps its interval:
+// any hit occludes, in any order.  What the loop leaves in a SpecRay follows
+// from the record: every accepted hit lies in [mint, best] and best shrinks to
+// it, so the last accepted rectangle is the best one (spec_init<RS_PRE>).
+// (a uniform trip count and selects: no exec-mask branches in the loop)
+DEV float4 rect_setup(const DevScene &S, float3 o, float3 d, float mint, float best, bool shadow, bool &tie) {
+    float4 rec = miss_record();
+    uint32_t bestKey = 0xFFFFFFFFu;   // no best yet (a first hit exactly at a finite maxt is flagged
+                                      // and traced again with the mailbox: the same answer)
+    tie = false;
+    const uint32_t nR = S.n_rect;
+    for (uint32_t k = 0; k < nR; ++k) {
+        const float4 *m = S.rectM + 3u * k;   // wave-uniform
+        float t, u, v;
+        const bool h = rect_test_rows(m[0], m[1], m[2], o, d, mint, best, t, u, v);
+        const uint32_t key = S.n_tri + k;
+        tie |= h & (t == best) & (key != bestKey);
+        bestKey = h ? key : bestKey;
+        best = (h & !shadow) ? t : best;
+        rec = h ? make_float4(t, u, v, __uint_as_float(0x80000000u | k)) : rec;
+    }
+    return rec;
+}
+
+// The pre-record of a ray as stored -- (o, mint), (d, maxt) and whether it is
+// a shadow ray: its interval, then the rectangle loop.  The one function of
+// "rectangles at setup": the trace refill runs it through spec_init<RS_LOOP>,
+// and the kernels that make rays (k_camera, k_shade) run it on the words they
+// store, so a record read back by spec_init<RS_PRE> is the one the refill
+// would have computed.  The tie flag rides in bit 30 of the record's last
+// word (a rectangle's local u, v lie in [-1, 1]: no sign bit is free; the
+// rectangle index is below MTSG_RECT_SETUP_CAP); a ray without an interval or
+// without a rectangle hit has the miss record.
+constexpr uint32_t PRE_TIE = 0x40000000u;
+DEV float4 ray_prerecord(const DevScene &S, float4 ro, float4 rd, bool shadow) {
+    const float3 o = xyz(ro), d = xyz(rd);
+    const float3 inv = mk3(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
+    float mint, best;
+    if (!ray_interval(S, o, d, inv, ro.w, rd.w, shadow, mint, best)) return miss_record();
+    bool tie;
+    float4 rec = rect_setup(S, o, d, mint, best, shadow, tie);
+    if (tie) rec.w = __uint_as_float(__float_as_uint(rec.w) | PRE_TIE);
+    return rec;
+}
+
+// spec_init's rectangle modes: none (the rectangles are leaf records), the
+// loop at the ray's setup, or its result read from the ray's pre-record
+enum { RS_NONE = 0, RS_LOOP = 1, RS_PRE = 2 };
+template <int RS = RS_NONE>
+DEV bool spec_init(const DevScene &S, float3 o, float3 d, float rayMint, float rayMaxt, bool shadow, SpecRay &r,
+                   float4 *hitOut = nullptr, float4 pre = make_float4(0.f, 0.f, 0.f, 0.f)) {
+    if (RS) r.bits = 0u;
+    r.o = o;
+    r.d = d;
+    r.inv = mk3(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
+    const uint32_t dneg = (d.x <= 0.0f ? 1u : 0u) | (d.y <= 0.0f ? 2u : 0u) | (d.z <= 0.0f ? 4u : 0u);
+    if (!ray_interval(S, o, d, r.inv, rayMint, rayMaxt, shadow, r.mint, r.best)) return false;
     r.tmin = r.mint;
     r.tmax = r.best;
     r.cur = S.root2;
@@ -890,31 +979,29 @@ DEV bool spec_init(const DevScene &S, float3 o, float3 d, float rayMint, float r
     r.lfTmax = -1.0f;
     r.bits = dneg << SB_DNEG | (shadow ? SB_SHADOW : 0u);
     r.mb = 0;
-    r.bestKey = 0xFFFFFFFFu;   // no best yet (a first hit exactly at a finite maxt is flagged
-                              // and traced again with the mailbox: the same answer)
+    r.bestKey = 0xFFFFFFFFu;   // no best yet
     if (RS) {
-        // a uniform trip count and selects: no exec-mask branches in the loop
-        // (a shadow ray keeps its interval: any hit occludes, in any order)
-        float4 rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        bool found = false;
-        const uint32_t nR = S.n_rect;
-        for (uint32_t k = 0; k < nR; ++k) {
-            const float4 *m = S.rectM + 3u * k;   // wave-uniform
-            float t, u, v;
-            const bool h = rect_test_rows(m[0], m[1], m[2], r.o, r.d, r.mint, r.best, t, u, v);
-            const uint32_t key = S.n_tri + k;
-            r.bits |= (h & (t == r.best) & (key != r.bestKey)) ? SB_TIE : 0u;
-            r.bestKey = h ? key : r.bestKey;
-            r.best = (h & !shadow) ? t : r.best;
-            rec = h ? make_float4(t, u, v, __uint_as_float(0x80000000u | k)) : rec;
-            found |= h;
+        // RS_PRE: the producer of the ray ran the same function on the same
+        // words (ray_prerecord), so rec and tie are what the loop gives here
+        bool tie;
+        float4 rec;
+        if (RS == RS_LOOP) {
+            rec = rect_setup(S, r.o, r.d, r.mint, r.best, shadow, tie);
+        } else {
+            rec = pre;
+            tie = (__float_as_uint(pre.w) & PRE_TIE) != 0u;
         }
-        if (found) {
+        const uint32_t w = __float_as_uint(rec.w);
+        if (w != 0xFFFFFFFFu) {
             if (shadow) {
                 r.bits = SB_FOUND;
                 return false;
             }
-            r.bits |= SB_FOUND;
+            const uint32_t k = w & ~(0x80000000u | PRE_TIE);
+            r.best = rec.x;
+            r.bestKey = S.n_tri + k;
+            r.bits |= SB_FOUND | (tie ? SB_TIE : 0u);
+            rec.w = __uint_as_float(0x80000000u | k);
             stS(hitOut, rec);
         }
     }
@@ -1240,12 +1327,16 @@ DEV bool spec_iter(const DevScene &S, SpecRay &r, SpecStack stk, TraceCounts &cn
 // the camera's, and mint / maxt are the same products k_camera formed (near /
 // far clip x 1/z), so the ray is bit for bit the one it used to store; a dead
 // slot (1/z = -1) keeps a negative maxt
+// (camera_ray_decode: also k_camera's, for the pre-record of the ray it stores)
+DEV void camera_ray_decode(const DevScene &S, float4 &ro, float4 &rd) {
+    const float invZ = rd.w;
+    ro = make_float4(S.camO[0], S.camO[1], S.camO[2], S.camNear * invZ);
+    rd.w = S.camFar * invZ;
+}
 DEV void load_closest_ray(const DevScene &S, const DevPaths &P, uint32_t idx, bool cam, float4 &ro, float4 &rd) {
     rd = ldS(P.ray_d + idx);
     if (cam) {
-        const float invZ = rd.w;
-        ro = make_float4(S.camO[0], S.camO[1], S.camO[2], S.camNear * invZ);
-        rd.w = S.camFar * invZ;
+        camera_ray_decode(S, ro, rd);
     } else {
         ro = ldS(P.ray_o + idx);
     }
@@ -1970,7 +2061,7 @@ DEV uint32_t shuffle_index(uint32_t x, uint32_t n) {
 
 // (the kernel's body: k_trace_s below, and under MTSG_FLAT_REGS its flat
 // specialisations with their own register budget in trace_flat.hip)
-template <bool COUNT, int MIN_IDLE, bool INST, bool KNOBS, bool LEAF_RECTS = false>
+template <bool COUNT, int MIN_IDLE, bool INST, bool KNOBS, bool LEAF_RECTS = false, bool PRE = false>
 DEV void trace_s_body(const DevScene &S, const DevPaths &P, int cIn, int sIn, uint32_t nIdentity, unsigned long long *wt) {
     const SpecStack stk{};
     const TravLimits L = trav_limits<KNOBS>(S);
@@ -1979,6 +2070,10 @@ DEV void trace_s_body(const DevScene &S, const DevPaths &P, int cIn, int sIn, ui
     // k_trace_s_leaf (LEAF_RECTS), the kernel of the scenes that keep the
     // in-leaf test
     constexpr bool RS = RECT_SETUP && !INST && !KNOBS && !LEAF_RECTS;
+    // PRE (k_trace_s_pre): the launch's closest rays carry pre-records (P.pre)
+    // and its shadow rays passed the rectangles where they were made, so the
+    // refill applies the record and runs no rectangle loop
+    constexpr int RSI = !RS ? RS_NONE : PRE ? RS_PRE : RS_LOOP;
     lds_top_init(S);
     const unsigned long long tStart = wt ? wall_clock64() : 0ull;
     const uint32_t nC = cIn == -1 ? nIdentity : (cIn >= 0 ? __atomic_load_n(&P.cnt[cnt_q(cIn)], __ATOMIC_RELAXED) : 0u);
@@ -2071,15 +2166,17 @@ DEV void trace_s_body(const DevScene &S, const DevPaths &P, int cIn, int sIn, ui
                 // measurement: the work list in a random order (coherence experiment)
                 if (!shadow || MTSG_SHUFFLE == 2) idx = shuffle_index(idx, shadow ? nS : nC);
 #endif
-                float4 ro, rd;
+                float4 ro, rd, pre = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (shadow) {
                     ro = ldS(P.sh_o + idx);
                     rd = ldS(P.sh_d + idx);
                     const float mint = rd.w; rd.w = ro.w; ro.w = mint;   // sh_o.w = maxt, sh_d.w = mint
+                    if (RSI == RS_PRE) pre = miss_record();   // (its producer dropped the rays a rectangle occludes)
                 } else {
+                    if (RSI == RS_PRE) pre = ldS(P.pre + idx);
                     load_closest_ray(S, P, idx, !INST && P.camEnc != 0, ro, rd);   // (two-level scenes: never compact)
                 }
-                if (spec_init<RS>(S, xyz(ro), xyz(rd), ro.w, rd.w, shadow, r, P.hit + idx)) {
+                if (spec_init<RSI>(S, xyz(ro), xyz(rd), ro.w, rd.w, shadow, r, P.hit + idx, pre)) {
                     active = true;
                     if (COUNT) {
                         iters = 0;
@@ -2202,6 +2299,14 @@ __global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_e
 k_trace_s_leaf(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned long long *wt) {
     trace_s_body<COUNT, MIN_IDLE, false, false, true>(S, P, cIn, sIn, nIdentity, wt);
 }
+// The setup-mode flat traversal over rays that carry pre-records (DevPaths::pre,
+// FlatTraceLaunch::pre): k_trace_s<COUNT, MIN_IDLE> without the rectangle loop
+// in its refill.  The path integrator's launches on flat scenes within the cap.
+template <bool COUNT, int MIN_IDLE>
+__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(MTSG_SPEC_WAVES)))
+k_trace_s_pre(DevScene S, DevPaths P, int cIn, int sIn, uint32_t nIdentity, unsigned long long *wt) {
+    trace_s_body<COUNT, MIN_IDLE, false, false, false, true>(S, P, cIn, sIn, nIdentity, wt);
+}
 
 // ---------------------------------------------------------------------------
 // camera rays (PerspectiveCamera::sampleRayDifferential, perspective.cpp:271-298)
@@ -2282,7 +2387,11 @@ DEV uint4 camera_meta(const DevBatch &B, uint32_t slot) {
     return alive ? make_uint4(1u, 2u + 2u * B.sensorDraws, slot, 1u + B.sensorDraws) : make_uint4(0u, 0u, slot, 0u);
 }
 
-__global__ void __launch_bounds__(BLOCK) k_camera(DevCamera C, DevIntegrator I, DevBatch B, DevPaths P) {
+// PRE (flat scenes in the setup mode, MTSG_OPT_RAY_PRESETUP 1): the pre-record
+// of every slot's ray into P.pre, of the ray as load_closest_ray hands it to
+// the traversal (ray_prerecord)
+template <bool PRE>
+__global__ void __launch_bounds__(BLOCK) k_camera(DevScene S, DevCamera C, DevIntegrator I, DevBatch B, DevPaths P) {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     bool alive = false;
     if (slot < B.nslots) {
@@ -2301,12 +2410,18 @@ __global__ void __launch_bounds__(BLOCK) k_camera(DevCamera C, DevIntegrator I, 
             // flat scenes: the direction and 1/z only (load_closest_ray: C3 / C5
             // k_camera 32 -> 16 B per path); two-level scenes keep the origin for
             // their instance exits and tie retraces
+            float4 ro, rd;
             if (C.compact) {
-                stS(&P.ray_d[slot], make_float4(wd.x, wd.y, wd.z, invZ));
+                rd = make_float4(wd.x, wd.y, wd.z, invZ);
+                stS(&P.ray_d[slot], rd);
+                if (PRE) camera_ray_decode(S, ro, rd);
             } else {
-                stS(&P.ray_o[slot], make_float4(C.c2w[3], C.c2w[7], C.c2w[11], C.near_clip * invZ));
-                stS(&P.ray_d[slot], make_float4(wd.x, wd.y, wd.z, C.far_clip * invZ));
+                ro = make_float4(C.c2w[3], C.c2w[7], C.c2w[11], C.near_clip * invZ);
+                rd = make_float4(wd.x, wd.y, wd.z, C.far_clip * invZ);
+                stS(&P.ray_o[slot], ro);
+                stS(&P.ray_d[slot], rd);
             }
+            if (PRE) stS(&P.pre[slot], ray_prerecord(S, ro, rd, false));
             if (C.diffs && !I.om) {   // myPath2_OM uses sensor->sampleRay: no differentials
                 float3 rxs, rys;
                 camera_differentials(C, I, nearP, wd, rxs, rys);
@@ -2323,8 +2438,10 @@ __global__ void __launch_bounds__(BLOCK) k_camera(DevCamera C, DevIntegrator I, 
             // one 2D request
             if (I.om) stS(&P.meta[slot], jitter ? make_uint4(1u, 2u, slot, 1u) : make_uint4(1u, 0u, slot, 0u));
         } else {
-            // dead slot: bounce 0 runs over all slots and skips it
+            // dead slot: bounce 0 runs over all slots and skips it (its
+            // negative maxt leaves no interval: the pre-record is not read)
             stS(&P.ray_d[slot], make_float4(0.f, 0.f, 1.f, -1.0f));
+            if (PRE) stS(&P.pre[slot], miss_record());
             if (I.om) stS(&P.meta[slot], make_uint4(0u, 0u, slot, 0u));
             stS(&P.L[slot], make_float4(0.f, 0.f, 0.f, 0.f));
         }
@@ -2382,7 +2499,8 @@ DEV void lens_ray(const DevCamera &C, const DevIntegrator &I, int x, int y, floa
 // dimension 4, camera_meta); the ray keeps its own origin, so it is stored
 // like a two-level scene's (ray_o / ray_d, DevScene::camCompact = 0), and
 // its differentials are always carried (DevScene::cam_diffs), never recomputed
-__global__ void __launch_bounds__(BLOCK) k_camera_lens(DevCamera C, DevIntegrator I, DevBatch B, DevPaths P) {
+template <bool PRE>
+__global__ void __launch_bounds__(BLOCK) k_camera_lens(DevScene S, DevCamera C, DevIntegrator I, DevBatch B, DevPaths P) {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= B.nslots) return;
     int x, y;
@@ -2410,10 +2528,12 @@ __global__ void __launch_bounds__(BLOCK) k_camera_lens(DevCamera C, DevIntegrato
         }
         stS(&P.ray_o[slot], ro);
         stS(&P.ray_d[slot], rd);
+        if (PRE) stS(&P.pre[slot], ray_prerecord(S, ro, rd, false));   // as k_camera's
     } else {
         // dead slot, as k_camera's: a negative maxt
         stS(&P.ray_o[slot], make_float4(0.f, 0.f, 0.f, 0.f));
         stS(&P.ray_d[slot], make_float4(0.f, 0.f, 1.f, -1.0f));
+        if (PRE) stS(&P.pre[slot], miss_record());
         stS(&P.L[slot], make_float4(0.f, 0.f, 0.f, 0.f));
     }
 }
@@ -4299,7 +4419,11 @@ DEV uint32_t shade_sort(uint32_t cls, uint32_t *cnt, uint16_t *perm) {
 // lookup of a primary miss, hideEmitters' camera case), 0 = later bounces only
 // (that code compiled out: C5's kernel then holds 96 VGPRs without spilling),
 // 2 = either (run-time)
-template <int ENV, int SMP, int EXT, int MATS = MATS_ALL, int FIRST = 2>
+// PRE: the launch writes the pre-records of the rays it makes (P.pre, flat
+// scenes in the setup mode with MTSG_OPT_RAY_PRESETUP 1).  A template
+// parameter and not a test of P.pre: the tests' registers in the kernel cost
+// the launches that do not run them 0.5 ms of C3's 27 (profiles/ray_presetup_ab.txt)
+template <int ENV, int SMP, int EXT, int MATS = MATS_ALL, int FIRST = 2, bool PRE = false>
 __global__ void SHADE_ATTR(ENV, MATS) k_shade(DevScene S, DevIntegrator I, DevBatch B, DevPaths P, int bounce, int qin,
                                                  uint32_t nIdentity, int hasAlpha) {
     __shared__ BlockAppend ba;
@@ -4372,6 +4496,16 @@ __global__ void SHADE_ATTR(ENV, MATS) k_shade(DevScene S, DevIntegrator I, DevBa
         // in registers live across its barriers.
         const int tid = threadIdx.x;
         uint32_t is, ic;
+        // PRE (flat scenes in the setup mode): the rectangles are tested
+        // here, for every live lane of the wave, on the rows staged in LDS --
+        // the words stage_write_* stores, so the traversal's own setup would
+        // compute the same (ray_prerecord).  A shadow ray that a rectangle
+        // occludes is not emitted: its contribution would never arrive.
+        if (PRE && shadow) {
+            const float4 so = stage.p[tid], sd = stage.shd[tid];   // sh_o.w = maxt; sh_d.w = mint = kEpsilon
+            const float4 rec = ray_prerecord(S, make_float4(so.x, so.y, so.z, kEpsilon), make_float4(sd.x, sd.y, sd.z, so.w), true);
+            shadow = __float_as_uint(rec.w) == 0xFFFFFFFFu;
+        }
 #if MTSG_SORT_OCT
         const float4 nd = stage.d[tid];
         const uint32_t key = (nd.x < 0.f ? 1u : 0u) | (nd.y < 0.f ? 2u : 0u) | (nd.z < 0.f ? 4u : 0u);
@@ -4380,7 +4514,13 @@ __global__ void SHADE_ATTR(ENV, MATS) k_shade(DevScene S, DevIntegrator I, DevBa
         block_append2(ba, &P.cnt[cnt_s(bounce & 1)], &P.cnt[cnt_q(qout)], shadow, cont, is, ic);
 #endif
         // survivor: compacted into the next bounce's arrays
-        if (cont) stage_write_next(stage, P, tid, ic, slot);
+        if (cont) {
+            stage_write_next(stage, P, tid, ic, slot);
+            if (PRE) {
+                const float4 p = stage.p[tid], d = stage.d[tid];
+                stS(&P.pre[ic], ray_prerecord(S, make_float4(p.x, p.y, p.z, kEpsilon), make_float4(d.x, d.y, d.z, INFINITY), false));
+            }
+        }
         if (shadow) stage_write_shadow(stage, P, tid, is, cont ? ic : (0x80000000u | slot));
     }
 }

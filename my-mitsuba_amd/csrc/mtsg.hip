@@ -39,6 +39,14 @@
 #include "kernels.h"
 #include "render_plan.h"
 
+// the default of MTSG_OPT_RAY_PRESETUP.  0: measured on C3, the producers' tests
+// and the 16 B per ray cost more than the refill saves (shade +4.4 ms, camera
+// +0.8, trace -3.7 of 129; profiles/ray_presetup_ab.txt).  1: a build for A/B
+// runs of a benchmark that sets no options.
+#ifndef MTSG_RAY_PRESETUP
+#define MTSG_RAY_PRESETUP 0
+#endif
+
 static_assert(PLAN_TILE == TILE, "render_plan.h plans in tiles of kernels.h's edge");
 
 namespace {
@@ -139,6 +147,10 @@ struct mtsg_scene {
     // and the scene can take it (at most RECT_SETUP_CAP rectangles, keyed
     // n_triangles + index); else the kernels that test them in the leaves
     bool rectSetupOpt = true, rectSetupOk = false;
+    // ... and in that mode, on request, the kernels that make the path
+    // integrator's rays (k_camera, k_shade) run those tests and leave each ray's
+    // pre-record for the refill (MTSG_OPT_RAY_PRESETUP; DevPaths::pre)
+    bool rayPresetupOpt = MTSG_RAY_PRESETUP != 0;
     mtsg_stats stats{};
     std::vector<hipEvent_t> evPool;
     size_t evUsed = 0;
@@ -213,7 +225,10 @@ void free_batch(mtsg_scene *s) {
 }
 
 int ensure_batch(mtsg_scene *s, uint32_t paths, int lanes) {
-    if (s->capacity >= paths && s->lanesAlloc >= lanes) return MTSG_OK;
+    // the order buffer (k_sortwin) and the pre-records only once
+    // MTSG_OPT_RAY_ORDER 1 / MTSG_OPT_RAY_PRESETUP 1 ask for them
+    const bool order = s->rayOrder == 1 || s->LP[0].orderBuf, pre = s->rayPresetupOpt || s->LP[0].preBuf;
+    if (s->capacity >= paths && s->lanesAlloc >= lanes && (!order || s->LP[0].orderBuf) && (!pre || s->LP[0].preBuf)) return MTSG_OK;
     paths = std::max(paths, s->capacity);
     lanes = std::max(lanes, s->lanesAlloc);
     free_batch(s);
@@ -232,7 +247,9 @@ int ensure_batch(mtsg_scene *s, uint32_t paths, int lanes) {
     A(hit, float4); A(L, float4); A(sh_o, float4); A(sh_d, float4); A(sh_c, float4);
     if (s->ds.inst) { A(hitInst, uint32_t); } else P.hitInst = nullptr;
     A(tie, uint32_t);
-    A(orderBuf, uint32_t);
+    if (pre) { A(preBuf, float4); } else P.preBuf = nullptr;
+    P.pre = nullptr;
+    if (order) { A(orderBuf, uint32_t); } else P.orderBuf = nullptr;
     P.order = nullptr;
 #undef A
     if ((rc = alloc(CNT_WORDS * sizeof(uint32_t), (void **)&P.cnt)) != MTSG_OK) return rc;
@@ -306,7 +323,7 @@ void timed_launch(mtsg_scene *s, int kind, hipStream_t st, F f) {
 // shadow rays sIn.  traceMode 1 refills lanes at 32 idle lanes instead of 16
 // (MTSG_TRACE_MODE, for measurement).
 template <bool COUNT>
-void launch_trace_c(mtsg_scene *s, const DevPaths &P, int cIn, int sIn, uint32_t n, hipStream_t st) {
+void launch_trace_c(mtsg_scene *s, const DevPaths &P, int cIn, int sIn, uint32_t n, hipStream_t st, bool pre) {
     dim3 g(s->traceGrid), blk(TRACE_BLOCK);
     unsigned long long *wt = nullptr;
     if ((s->flags & MTSG_FLAG_WAVETIME) && s->waveTimes && s->wtLaunches < WT_MAX_LAUNCHES && !s->ds.inst)
@@ -319,7 +336,7 @@ void launch_trace_c(mtsg_scene *s, const DevPaths &P, int cIn, int sIn, uint32_t
     const dim3 tg(std::max<unsigned>(1u, (unsigned)s->traceGrid / 4u));
     if (!s->ds.inst) {   // the flat kernels: trace_flat.hip
         FlatTraceLaunch a{g, tg, st, &s->ds, &P, cIn, sIn, n, wt, COUNT, s->knobs, s->traceMode == 1,
-                          MTSG_MAILBOX && cIn != -2 && !TIE_INLINE, s->rectSetupOpt && s->rectSetupOk};
+                          MTSG_MAILBOX && cIn != -2 && !TIE_INLINE, s->rectSetupOpt && s->rectSetupOk, pre};
         launch_trace_flat(a);
         return;
     }
@@ -328,9 +345,15 @@ void launch_trace_c(mtsg_scene *s, const DevPaths &P, int cIn, int sIn, uint32_t
     else hipLaunchKernelGGL((k_trace_s<COUNT, MTSG_INST_MIN_IDLE, true>), dim3(s->traceGridInst), blk, 0, st, s->ds, P, cIn, sIn, n, wt);
     if (MTSG_MAILBOX && cIn != -2) hipLaunchKernelGGL(k_tie_i, tg, blk, 0, st, s->ds, P);
 }
-void launch_trace(mtsg_scene *s, bool count, const DevPaths &P, int cIn, int sIn, uint32_t n, hipStream_t st) {
-    if (count) launch_trace_c<true>(s, P, cIn, sIn, n, st);
-    else launch_trace_c<false>(s, P, cIn, sIn, n, st);
+// pre: the rays carry pre-records (P.pre; FlatTraceLaunch::pre)
+void launch_trace(mtsg_scene *s, bool count, const DevPaths &P, int cIn, int sIn, uint32_t n, hipStream_t st, bool pre = false) {
+    if (count) launch_trace_c<true>(s, P, cIn, sIn, n, st, pre);
+    else launch_trace_c<false>(s, P, cIn, sIn, n, st, pre);
+}
+// whether a handle's flat traversal launches can take pre-records at all: the
+// setup mode is on and applies, and the test knobs' kernel is not in use
+bool presetup_applies(const mtsg_scene *s) {
+    return s->rayPresetupOpt && s->rectSetupOpt && s->rectSetupOk && !s->ds.inst && !s->knobs;
 }
 
 // k_shade / k_finish are instantiated per sampler in smp_kernels.hip
@@ -573,7 +596,7 @@ uint32_t fit_paths(const mtsg_scene *s, size_t stateBytes) {
     uint32_t maxPaths = DEFAULT_BATCH_PATHS;
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-        const size_t held = (size_t)s->capacity * s->lanesAlloc * PATH_STATE_BYTES + (size_t)s->fieldCap * s->fieldCount * 3 * sizeof(float) +
+        const size_t held = (size_t)s->capacity * s->lanesAlloc * (PATH_STATE_BYTES + (s->LP[0].orderBuf ? PATH_ORDER_BYTES : 0) + (s->LP[0].preBuf ? PATH_PRE_BYTES : 0)) + (size_t)s->fieldCap * s->fieldCount * 3 * sizeof(float) +
                             s->fanClosest * FAN_CLOSEST_BYTES + s->fanShadow * FAN_SHADOW_BYTES;
         // 3/4 of the free HBM (288 GB on an MI355X: 768M paths, C5's three
         // batches of 713M); the rest stays for the scene and other users
@@ -604,6 +627,10 @@ struct RenderRun {
     bool fieldsOnly = false;   // multichannel without a `path` child
     bool useFinish = false;    // tail mode (k_finish)
     bool direct = false;       // direct / ao: camera rays, the fan, resolve (direct.hip)
+    // the `path` integrator on a flat scene in the setup mode: k_camera and
+    // k_shade write each ray's pre-record and the trace launches read it.  Not
+    // the multichannel, direct / ao and myPath2_OM routes: their rays carry none.
+    bool pre = false;
     int blockW = 0, blockH = 0, maxBounces = 0;
     struct Lane {
         DevBatch B;
@@ -688,10 +715,13 @@ struct RenderRun {
         hipStream_t st = s->lstream[l];
         if (b == 0) {
             HIP_TRY(hipMemsetAsync(P.cnt, 0, CNT_WORDS * sizeof(uint32_t), st));
+            P.pre = pre ? P.preBuf : nullptr;
             timed_launch(s, K_CAMERA, st, [&]() {
                 const dim3 g((L.B.nslots + BLOCK - 1) / BLOCK);
-                if (s->cam.lens) hipLaunchKernelGGL(k_camera_lens, g, dim3(BLOCK), 0, st, s->cam, I, L.B, P);
-                else hipLaunchKernelGGL(k_camera, g, dim3(BLOCK), 0, st, s->cam, I, L.B, P);
+                if (s->cam.lens && pre) hipLaunchKernelGGL(k_camera_lens<true>, g, dim3(BLOCK), 0, st, s->ds, s->cam, I, L.B, P);
+                else if (s->cam.lens) hipLaunchKernelGGL(k_camera_lens<false>, g, dim3(BLOCK), 0, st, s->ds, s->cam, I, L.B, P);
+                else if (pre) hipLaunchKernelGGL(k_camera<true>, g, dim3(BLOCK), 0, st, s->ds, s->cam, I, L.B, P);
+                else hipLaunchKernelGGL(k_camera<false>, g, dim3(BLOCK), 0, st, s->ds, s->cam, I, L.B, P);
             });
         }
         const int qin = b == 0 ? -1 : (b & 1);
@@ -707,7 +737,7 @@ struct RenderRun {
             });
             PT.order = P.orderBuf;
         }
-        timed_launch(s, K_CLOSEST, st, [&]() { launch_trace(s, count, PT, qin, b == 0 ? -1 : ((b - 1) & 1), L.B.nslots, st); });
+        timed_launch(s, K_CLOSEST, st, [&]() { launch_trace(s, count, PT, qin, b == 0 ? -1 : ((b - 1) & 1), L.B.nslots, st, pre); });
         if (multi && b == 0) {
             // the bounce-0 hits are final (the tie retrace is part of the trace
             // launch) and the work list is the identity: the field children
@@ -768,7 +798,7 @@ struct RenderRun {
         hipStream_t st = s->lstream[l];
         if (L.last >= 0 && !L.finished) {
             hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, st, P.cnt, -1, -1);
-            timed_launch(s, K_SHADOW, st, [&]() { launch_trace(s, count, P, -2, L.last & 1, 0u, st); });
+            timed_launch(s, K_SHADOW, st, [&]() { launch_trace(s, count, P, -2, L.last & 1, 0u, st, pre); });
             s->stats.launches_trace_shadow++;
             // the error word again, after this launch: a traversal error of
             // the last bounce's shadow rays fails the render too (the copy
@@ -1013,7 +1043,8 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
     fan_counts(s, p, ne, nb);
     // bytes of state per path: the field planes join it while fields are
     // active, the fan's rays and cells in a direct / ao render
-    const uint32_t maxPaths = fit_paths(s, PATH_STATE_BYTES + (multi ? (size_t)s->aov.nf * 3 * sizeof(float) : 0) + fan_bytes(ne, nb));
+    const uint32_t maxPaths = fit_paths(s, PATH_STATE_BYTES + (s->rayOrder == 1 || s->LP[0].orderBuf ? PATH_ORDER_BYTES : 0) +
+                                               (s->rayPresetupOpt || s->LP[0].preBuf ? PATH_PRE_BYTES : 0) + (multi ? (size_t)s->aov.nf * 3 * sizeof(float) : 0) + fan_bytes(ne, nb));
     if ((s->dumpL || s->dumpMulti) && (uint64_t)p->tile_w * p->tile_h * p->spp > maxPaths) { g_err = "render_samples: tile does not fit one batch"; return MTSG_ERR_INVALID; }
     // The debug and counting modes use one lane (multichannel too: one set of
     // field planes; direct / ao: one set of fan buffers)
@@ -1068,6 +1099,7 @@ int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win
     // tail mode (k_finish): one lane, not in the instrumented or myPath2_OM modes
     R.useFinish = s->finishPaths > 0 && R.plan.lanes == 1 && !count && !I.om && !s->knobs && !direct;
     R.direct = direct;
+    R.pre = presetup_applies(s) && !multi && !direct && !I.om;
     if (direct) R.maxBounces = 1;
     rc = R.open_lanes();
     if (rc == MTSG_OK) rc = R.run_batches();
@@ -1830,6 +1862,10 @@ int mtsg_set_option(mtsg_scene *s, int32_t key, int64_t value) {
             if (value < 0 || value > 1) { g_err = "MTSG_OPT_RECT_SETUP: 0 (rectangles tested in the leaves) or 1 (at ray setup)"; return MTSG_ERR_INVALID; }
             s->rectSetupOpt = value != 0;
             return MTSG_OK;
+        case MTSG_OPT_RAY_PRESETUP:
+            if (value < 0 || value > 1) { g_err = "MTSG_OPT_RAY_PRESETUP: 0 (rectangles tested in the traversal's refill) or 1 (where the rays are made)"; return MTSG_ERR_INVALID; }
+            s->rayPresetupOpt = value != 0;
+            return MTSG_OK;
         default:
             g_err = "unknown option key " + std::to_string(key);
             return MTSG_ERR_INVALID;
@@ -2082,8 +2118,30 @@ int mtsg_render_samples(mtsg_scene *s, const mtsg_render_params *p, float *L_out
     return render_samples(s, p, L_out, false);
 }
 
+// The producer's part of a ray query in the pre-record mode, what k_camera and
+// k_shade do for the rays they make: a closest ray's pre-record into P.pre; a
+// shadow ray of list Q is appended to P's list (CNT_S0) unless a rectangle
+// occludes it (its cell then keeps "occluded": no contribution arrives).
+static __global__ void k_query_pre(DevScene S, DevPaths P, DevPaths Q, uint32_t n, int shadow) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!shadow) {
+        stS(&P.pre[i], ray_prerecord(S, ldS(P.ray_o + i), ldS(P.ray_d + i), false));
+        return;
+    }
+    const float4 so = ldS(Q.sh_o + i), sd = ldS(Q.sh_d + i);   // sh_o.w = maxt, sh_d.w = mint
+    const float4 rec = ray_prerecord(S, make_float4(so.x, so.y, so.z, sd.w), make_float4(sd.x, sd.y, sd.z, so.w), true);
+    if (__float_as_uint(rec.w) != 0xFFFFFFFFu) return;
+    const uint32_t j = atomicAdd(&P.cnt[CNT_S0], 1u);
+    stS(&P.sh_o[j], so);
+    stS(&P.sh_d[j], sd);
+    stS(&P.sh_c[j], ldS(Q.sh_c + i));
+}
+
 // Ray queries run the production traversal kernel (the one the integrator
-// launches, selected by traceMode) over a work list of n rays.
+// launches, selected by traceMode) over a work list of n rays; with
+// MTSG_OPT_RAY_PRESETUP 1, where it applies, as the path integrator runs it:
+// over rays with pre-records (k_query_pre).
 static int trace_rays(mtsg_scene *s, uint32_t n, const float *rays, float *t, float *u, float *v, uint32_t *prim,
                       uint8_t *occ, bool shadow) {
     if (!s || (!rays && n)) return MTSG_ERR_INVALID;
@@ -2129,10 +2187,18 @@ static int trace_rays(mtsg_scene *s, uint32_t n, const float *rays, float *t, fl
     D.tie = tie.p;
     D.cnt = cnt.p;
     D.ctr = ctr.p;
-    if (e == hipSuccess && shadow) e = hipMemcpy(D.cnt + CNT_S0, &n, sizeof(uint32_t), hipMemcpyHostToDevice);
+    const bool pre = presetup_applies(s);
+    DevBuf<float4> dpre(e, pre && !shadow ? n : 0), da2(e, pre && shadow ? n : 0), db2(e, pre && shadow ? n : 0), dc2(e, pre && shadow ? n : 0);
+    if (e == hipSuccess && shadow && !pre) e = hipMemcpy(D.cnt + CNT_S0, &n, sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) { g_err = hipGetErrorString(e); return MTSG_ERR_DEVICE; }
-    if (shadow) launch_trace(s, false, D, -2, 0, 0u, s->stream);
-    else launch_trace(s, false, D, -1, -1, n, s->stream);
+    if (pre) {
+        const DevPaths Q = D;
+        if (shadow) { D.sh_o = da2.p; D.sh_d = db2.p; D.sh_c = dc2.p; }
+        else D.pre = dpre.p;
+        hipLaunchKernelGGL(k_query_pre, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, D, Q, n, shadow ? 1 : 0);
+    }
+    if (shadow) launch_trace(s, false, D, -2, 0, 0u, s->stream, pre);
+    else launch_trace(s, false, D, -1, -1, n, s->stream, pre);
     e = hipStreamSynchronize(s->stream);
     if (e == hipSuccess) e = hipGetLastError();
     dout.download(out.data());
@@ -2449,8 +2515,8 @@ int mtsg_camera_rays(mtsg_scene *s, const mtsg_render_params *p, uint32_t n, con
         P.ray_o = ro.p; P.ray_d = rd.p; P.T = T.p; P.aux = aux.p; P.L = L.p; P.meta = meta.p;
         P.camEnc = s->ds.camCompact ? 1u : 0u;
         const dim3 g((nslots + BLOCK - 1) / BLOCK);
-        if (cam.lens) hipLaunchKernelGGL(k_camera_lens, g, dim3(BLOCK), 0, s->stream, cam, I, B, P);
-        else hipLaunchKernelGGL(k_camera, g, dim3(BLOCK), 0, s->stream, cam, I, B, P);
+        if (cam.lens) hipLaunchKernelGGL(k_camera_lens<false>, g, dim3(BLOCK), 0, s->stream, s->ds, cam, I, B, P);
+        else hipLaunchKernelGGL(k_camera<false>, g, dim3(BLOCK), 0, s->stream, s->ds, cam, I, B, P);
         hipLaunchKernelGGL(k_camera_rays_read, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ds, P, dslots.p, n, dout.p);
         e = hipStreamSynchronize(s->stream);
     }

@@ -11,12 +11,24 @@
 
 namespace mtsg {
 
+// one k_shade launch: the instantiation that writes pre-records when the
+// launch's paths carry them (ShadeLaunch::P->pre), else the plain one
+#define SHADE_LAUNCH(a, ENV, SMP, EXT, MATS, FIRST)                                                                                  \
+    do {                                                                                                                             \
+        if ((a).P->pre)                                                                                                              \
+            hipLaunchKernelGGL((k_shade<ENV, SMP, EXT, MATS, FIRST, true>), (a).grid, (a).block, 0, (a).stream, *(a).S, *(a).I, *(a).B, \
+                               *(a).P, (a).bounce, (a).qin, (a).nIdentity, (a).hasAlpha);                                           \
+        else                                                                                                                         \
+            hipLaunchKernelGGL((k_shade<ENV, SMP, EXT, MATS, FIRST>), (a).grid, (a).block, 0, (a).stream, *(a).S, *(a).I, *(a).B,    \
+                               *(a).P, (a).bounce, (a).qin, (a).nIdentity, (a).hasAlpha);                                           \
+    } while (0)
+
 #ifdef MTSG_TU_EXT2
 // this sampler's kernels for scenes with a phong, ward, roughdiffuse, difftrans
 // or thindielectric record: every emitter kind and every BSDF (EXT level 2)
 template <>
 void launch_shade_ext2<MTSG_TU_SAMPLER>(const ShadeLaunch &a) {
-    hipLaunchKernelGGL((k_shade<EM_ALL, MTSG_TU_SAMPLER, 2>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
+    SHADE_LAUNCH(a, EM_ALL, MTSG_TU_SAMPLER, 2, MATS_ALL, 2);
 }
 template <>
 void launch_finish_ext2<MTSG_TU_SAMPLER>(const ShadeLaunch &a) {
@@ -30,14 +42,14 @@ void launch_finish_ext2<MTSG_TU_SAMPLER>(const ShadeLaunch &a) {
 template <int SMP, int MATS>
 void launch_shade_mats(const ShadeLaunch &a) {
     if constexpr (MATS == MATS_ALL) {
-        if (a.env) hipLaunchKernelGGL((k_shade<true, SMP, false>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
-        else hipLaunchKernelGGL((k_shade<false, SMP, false>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
+        if (a.env) SHADE_LAUNCH(a, true, SMP, false, MATS_ALL, 2);
+        else SHADE_LAUNCH(a, false, SMP, false, MATS_ALL, 2);
     } else if (a.bounce == 0) {
-        if (a.env) hipLaunchKernelGGL((k_shade<true, SMP, false, MATS, 1>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
-        else hipLaunchKernelGGL((k_shade<false, SMP, false, MATS, 1>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
+        if (a.env) SHADE_LAUNCH(a, true, SMP, false, MATS, 1);
+        else SHADE_LAUNCH(a, false, SMP, false, MATS, 1);
     } else {
-        if (a.env) hipLaunchKernelGGL((k_shade<true, SMP, false, MATS, 0>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
-        else hipLaunchKernelGGL((k_shade<false, SMP, false, MATS, 0>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
+        if (a.env) SHADE_LAUNCH(a, true, SMP, false, MATS, 0);
+        else SHADE_LAUNCH(a, false, SMP, false, MATS, 0);
     }
 }
 
@@ -58,12 +70,12 @@ void launch_shade_smp<MTSG_TU_SAMPLER>(const ShadeLaunch &a) {
         return;
     }
     if (a.emx) {
-        hipLaunchKernelGGL((k_shade<EM_ALL, SMP, true>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
+        SHADE_LAUNCH(a, EM_ALL, SMP, true, MATS_ALL, 2);
         return;
     }
     if (a.ext) {
-        if (a.env) hipLaunchKernelGGL((k_shade<true, SMP, true>),a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
-        else hipLaunchKernelGGL((k_shade<false, SMP, true>), a.grid, a.block, 0, a.stream, *a.S, *a.I, *a.B, *a.P, a.bounce, a.qin, a.nIdentity, a.hasAlpha);
+        if (a.env) SHADE_LAUNCH(a, true, SMP, true, MATS_ALL, 2);
+        else SHADE_LAUNCH(a, false, SMP, true, MATS_ALL, 2);
         return;
     }
     // the smallest compiled material set that holds the scene's (mats_kernel_set);

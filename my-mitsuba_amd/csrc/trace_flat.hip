@@ -8,6 +8,15 @@
 // only: the same IEEE operations, the same hits.
 // (kernels.h defines every kernel; this unit launches only the flat traversal)
 #pragma clang diagnostic ignored "-Wunused-function"
+// The flat kernels' short stack keeps the lane's index in a register, filled
+// once per kernel, instead of recomputing it with a v_mbcnt pair at every push
+// and pop (kernels.h SpecStack): 64 VGPRs from 61, still 8 waves/SIMD and no
+// scratch; C3 trace -2.3 ms of 100.7, with the pre-records on -2.1 of 97.0
+// (profiles/ray_presetup_ab.txt).  This unit only: the tail kernel and the
+// two-level traversal keep the recomputed index.
+#ifndef MTSG_STACK_LANE   // (-DMTSG_STACK_LANE=0: the recomputed index everywhere, for A/B runs)
+#define MTSG_STACK_LANE 1
+#endif
 #include "kernels.h"
 
 #if MTSG_FLAT_REGS
@@ -37,7 +46,12 @@ static void launch_flat(const FlatTraceLaunch &a) {
     // spec_init<true>); <.., false, true>, the test knobs' kernel, and
     // k_trace_s_leaf, the kernel of the scenes that do not take the setup mode
     // (a.rectSetup false): in the leaves.  The COUNT pass follows the timed kernel.
-    if (a.knobs && !COUNT) hipLaunchKernelGGL((k_trace_s<false, 16, false, true>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
+    // a.pre: the rays carry pre-records, the refill runs no rectangle loop
+    // (k_trace_s_pre; the launcher sets it only with a.rectSetup and without a.knobs)
+    if (a.pre && a.rectSetup && !a.knobs) {
+        if (a.refill32) hipLaunchKernelGGL((k_trace_s_pre<COUNT, 32>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
+        else hipLaunchKernelGGL((k_trace_s_pre<COUNT, 16>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
+    } else if (a.knobs && !COUNT) hipLaunchKernelGGL((k_trace_s<false, 16, false, true>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
     else if (!a.rectSetup && a.refill32) hipLaunchKernelGGL((k_trace_s_leaf<COUNT, 32>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
     else if (!a.rectSetup) hipLaunchKernelGGL((k_trace_s_leaf<COUNT, 16>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
     else if (a.refill32) hipLaunchKernelGGL((k_trace_s<COUNT, 32>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
