@@ -722,9 +722,16 @@ int  mtsg_set_finish_paths(mtsg_scene *scene, uint32_t paths);
  *                             rectangle occludes is not sent to it, so
  *                             mtsg_stats::rays_shadow counts the rays traced;
  *                             measured slower)
+ *   MTSG_OPT_LEAF_FILTER      flat scenes in that mode: 1 (default) = the timed
+ *                             traversal walks a second leaf addressing whose
+ *                             leaves hold no rectangle records (the rays tested
+ *                             the rectangles at their setup), 0 = it steps over
+ *                             those records in the scene's own leaves (A/B
+ *                             tests).  Counting renders (MTSG_FLAG_COUNT) always
+ *                             walk the scene's own leaves.
  * Unknown keys and values out of range return MTSG_ERR_INVALID. */
 /* the most rectangles a flat scene may hold for MTSG_OPT_RECT_SETUP 1 to apply */
-#define MTSG_RECT_SETUP_CAP 2u
+#define MTSG_RECT_SETUP_CAP 8u
 enum {
     MTSG_OPT_TRACE_REFILL = 1,
     MTSG_OPT_FINISH_SHADE_MIN = 2,
@@ -734,7 +741,8 @@ enum {
     MTSG_OPT_RAY_ORDER = 6,
     MTSG_OPT_CAMERA_DIFFS = 7,
     MTSG_OPT_RECT_SETUP = 8,
-    MTSG_OPT_RAY_PRESETUP = 9
+    MTSG_OPT_RAY_PRESETUP = 9,
+    MTSG_OPT_LEAF_FILTER = 10
 };
 int  mtsg_set_option(mtsg_scene *scene, int32_t key, int64_t value);
 

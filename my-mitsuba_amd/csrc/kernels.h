@@ -256,6 +256,14 @@ struct FlatTraceLaunch {
     // wrote them and dropped the shadow rays a rectangle occludes): the refill
     // runs no rectangle loop (k_trace_s_pre).  Only with rectSetup and without knobs.
     bool pre = false;
+    // the timed setup-mode kernels (k_trace_s<false, 16|32>, k_trace_s_pre<false, ..>)
+    // walk the filtered leaf addressing: blocksRS / root2RS in place of
+    // S->blocks / S->root2 (kd_layout.h: the same inner words, leaves without
+    // rectangle records).  The COUNT, KNOBS and in-leaf kernels and k_tie visit
+    // primitives in Mitsuba's order and keep S->blocks.
+    bool leafFilter = false;
+    const uint4 *blocksRS = nullptr;
+    uint2 root2RS = {0u, 0u};
 };
 void launch_trace_flat(const FlatTraceLaunch &a);
 int trace_flat_blocks_per_cu();   // k_trace_s<false, 16> workgroups per CU (occupancy query)

@@ -38,6 +38,7 @@
 
 #include "kernels.h"
 #include "render_plan.h"
+#include "kd_layout.h"
 
 // the default of MTSG_OPT_RAY_PRESETUP.  0: measured on C3, the producers' tests
 // and the 16 B per ray cost more than the refill saves (shade +4.4 ms, camera
@@ -45,6 +46,11 @@
 // runs of a benchmark that sets no options.
 #ifndef MTSG_RAY_PRESETUP
 #define MTSG_RAY_PRESETUP 0
+#endif
+// the default of MTSG_OPT_LEAF_FILTER (0: a build for A/B runs of a benchmark
+// that sets no options)
+#ifndef MTSG_LEAF_FILTER
+#define MTSG_LEAF_FILTER 1
 #endif
 
 static_assert(PLAN_TILE == TILE, "render_plan.h plans in tiles of kernels.h's edge");
@@ -151,6 +157,13 @@ struct mtsg_scene {
     // integrator's rays (k_camera, k_shade) run those tests and leave each ray's
     // pre-record for the refill (MTSG_OPT_RAY_PRESETUP; DevPaths::pre)
     bool rayPresetupOpt = MTSG_RAY_PRESETUP != 0;
+    // ... and in that mode the timed kernels walk the filtered leaf addressing
+    // (kd_layout.h blocksRS: no rectangle records in the leaves; null when no
+    // leaf references a rectangle) unless MTSG_OPT_LEAF_FILTER is 0.  Both
+    // layouts stay resident, so the option switches per launch.
+    bool leafFilterOpt = MTSG_LEAF_FILTER != 0;
+    const uint4 *blocksRS = nullptr;
+    uint2 root2RS{};
     mtsg_stats stats{};
     std::vector<hipEvent_t> evPool;
     size_t evUsed = 0;
@@ -337,6 +350,9 @@ void launch_trace_c(mtsg_scene *s, const DevPaths &P, int cIn, int sIn, uint32_t
     if (!s->ds.inst) {   // the flat kernels: trace_flat.hip
         FlatTraceLaunch a{g, tg, st, &s->ds, &P, cIn, sIn, n, wt, COUNT, s->knobs, s->traceMode == 1,
                           MTSG_MAILBOX && cIn != -2 && !TIE_INLINE, s->rectSetupOpt && s->rectSetupOk, pre};
+        a.leafFilter = s->leafFilterOpt && s->blocksRS != nullptr;
+        a.blocksRS = s->blocksRS;
+        a.root2RS = s->root2RS;
         launch_trace_flat(a);
         return;
     }
@@ -1240,158 +1256,33 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
         if (r == MTSG_OK && *dst) s->allocs.push_back((void *)*dst);
         return r;
     };
-    // ---- device kd-tree layout from Mitsuba's KDNode array (same splits and
-    // leaves, re-laid out): sibling pairs (host only, the input of the
-    // two-level blocks) + leaf-ordered TriAccel copies.  The top-level tree
-    // and every shape group's tree (two-level instancing) share both arrays.
-    std::vector<uint4> pairs;
-    std::vector<float4> triL;
-    pairs.reserve(d->n_nodes / 2 + 1);
-    triL.reserve((size_t)d->n_indices * 3);
-    bool layoutOk = true;
-    const mtsg_kdnode *tNodes = d->nodes;
-    const uint32_t *tIdx = d->indices;
-    uint32_t tNodeCount = d->n_nodes, tIdxCount = d->n_indices;
-    std::function<uint2(uint32_t, int)> convert = [&](uint32_t ni, int depth) -> uint2 {
-        if (depth > 64 || ni >= tNodeCount) { layoutOk = false; return make_uint2(0x80000000u, 0u); }
-        const mtsg_kdnode &N = tNodes[ni];
-        if (N.combined & 0x80000000u) {
-            const uint32_t start = (uint32_t)(triL.size() / 3);
-            for (uint32_t e = N.combined & 0x7FFFFFFFu; e < N.data; ++e) {
-                const uint32_t p = e < tIdxCount ? tIdx[e] : 0xFFFFFFFFu;
-                if (p >= d->n_prims) { layoutOk = false; break; }
-                mtsg_triaccel ta = d->triaccel[p];
-                if (ta.k == MTSG_TRIACCEL_SHAPE && ta.shape_index < d->n_shapes &&
-                    d->shapes[ta.shape_index].type == MTSG_SHAPE_INSTANCE) {
-                    if (ta.prim_index >= d->n_instances) { layoutOk = false; break; }
-                    ta.k = KINST;
-                    // the instance's world box in the record's free words
-                    // (n_u n_v n_d = min, a_u a_v b_nu = max): the group box's
-                    // corners through to_world in double, widened by 1e-4 of
-                    // its size and position and rounded outward, so the
-                    // traversal's prefilter (kernels.h inst_box) never drops an
-                    // entry the exact group-space clip would take
-                    const mtsg_instance &I = d->instances[ta.prim_index];
-                    if (I.group >= d->n_groups) { layoutOk = false; break; }
-                    const mtsg_group &G = d->groups[I.group];
-                    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-                    for (int c = 0; c < 8; ++c) {
-                        const double q[3] = {(c & 1) ? G.aabb_max[0] : G.aabb_min[0], (c & 2) ? G.aabb_max[1] : G.aabb_min[1],
-                                             (c & 4) ? G.aabb_max[2] : G.aabb_min[2]};
-                        for (int a = 0; a < 3; ++a) {
-                            const float *W = I.to_world + 4 * a;
-                            const double w = (double)W[0] * q[0] + (double)W[1] * q[1] + (double)W[2] * q[2] + (double)W[3];
-                            lo[a] = std::min(lo[a], w);
-                            hi[a] = std::max(hi[a], w);
-                        }
-                    }
-                    double ext = 0, mag = 0;
-                    for (int a = 0; a < 3; ++a) {
-                        ext = std::max(ext, hi[a] - lo[a]);
-                        mag = std::max(mag, std::max(std::fabs(lo[a]), std::fabs(hi[a])));
-                    }
-                    const double m = 1e-4 * (ext + mag) + 1e-30;
-                    float bmin[3], bmax[3];
-                    for (int a = 0; a < 3; ++a) {
-                        bmin[a] = std::nextafter((float)(lo[a] - m), -INFINITY);
-                        bmax[a] = std::nextafter((float)(hi[a] + m), INFINITY);
-                    }
-                    if (!std::isfinite(bmin[0] + bmin[1] + bmin[2] + bmax[0] + bmax[1] + bmax[2])) {
-                        // a degenerate or unbounded transform: a box that takes every ray
-                        for (int a = 0; a < 3; ++a) { bmin[a] = -INFINITY; bmax[a] = INFINITY; }
-                    }
-                    ta.n_u = bmin[0]; ta.n_v = bmin[1]; ta.n_d = bmin[2];
-                    ta.a_u = bmax[0]; ta.a_v = bmax[1]; ta.b_nu = bmax[2];
-                }
-                // the TriAccel index (Mitsuba's mailbox key, kernels.h
-                // mailbox_step) in place of the shape index
-                ta.shape_index = p;
-                const float4 *t = (const float4 *)&ta;
-                triL.push_back(t[0]); triL.push_back(t[1]); triL.push_back(t[2]);
-            }
-            return make_uint2(0x80000000u | start, (uint32_t)(triL.size() / 3));
-        }
-        const uint32_t left = ni + ((N.combined & ~(3u | 0x40000000u)) >> 2);
-        const uint32_t pi = (uint32_t)pairs.size();
-        pairs.push_back(make_uint4(0, 0, 0, 0));
-        const uint2 L = convert(left, depth + 1);
-        const uint2 R = convert(left + 1, depth + 1);
-        pairs[pi] = make_uint4(L.x, L.y, R.x, R.y);
-        return make_uint2((N.combined & 3u) | (pi << 2), N.data);
-    };
-    const uint2 root = convert(0, 0);
-    std::vector<uint2> groupRoots(d->n_groups);
-    if (d->n_instances && (!d->instances || !d->groups || !d->group_nodes || !d->group_indices)) layoutOk = false;
-    for (uint32_t g = 0; g < d->n_groups && layoutOk; ++g) {
-        const mtsg_group &G = d->groups[g];
-        if ((uint64_t)G.node_offset + G.n_nodes > d->n_group_nodes || (uint64_t)G.index_offset + G.n_indices > d->n_group_indices ||
-            G.n_nodes == 0) { layoutOk = false; break; }
-        tNodes = d->group_nodes + G.node_offset;
-        tIdx = d->group_indices + G.index_offset;
-        tNodeCount = G.n_nodes;
-        tIdxCount = G.n_indices;
-        groupRoots[g] = convert(0, 0);
+    // the setup mode names rectangle r by the tie key n_triangles + r, its
+    // TriAccel index in the leaf records: hold the description to that
+    s->rectSetupOk = MTSG_RECT_SETUP && d->n_rects <= RECT_SETUP_CAP;
+    for (uint32_t r = 0; r < d->n_rects && s->rectSetupOk; ++r) {
+        if (!d->triaccel || (uint64_t)d->n_triangles + r >= d->n_prims) { s->rectSetupOk = false; break; }
+        const mtsg_triaccel &ta = d->triaccel[d->n_triangles + r];
+        s->rectSetupOk = ta.k == MTSG_TRIACCEL_SHAPE && ta.prim_index == r && ta.shape_index < d->n_shapes &&
+                         d->shapes[ta.shape_index].type == MTSG_SHAPE_RECT;
     }
-    for (uint32_t i = 0; i < d->n_instances && layoutOk; ++i)
-        if (d->instances[i].group >= d->n_groups) layoutOk = false;
-    if (!layoutOk || pairs.size() >= (1u << 29) || triL.size() / 3 >= (1u << 30)) {
-        g_err = "malformed or oversized kd-tree";
+    // ---- device kd-tree layout from Mitsuba's KDNode array (kd_layout.h: host
+    // only).  A flat scene that takes the setup mode gets the filtered leaf
+    // addressing next to it (blocksRS; MTSG_OPT_LEAF_FILTER): this is the one
+    // place a handle's layout is made, so both arrays always come from the
+    // same tree (a replaced or refitted tree reaches the device as a new handle).
+    KdLayout lay;
+    if (const char *what = kd_layout(d, s->rectSetupOk && d->n_rects > 0 && d->n_instances == 0, lay)) {
+        g_err = what;
         return fail(MTSG_ERR_INVALID);
     }
-    // ---- two-level blocks from the binary pair layout
-    std::vector<uint4> blocks;
-    blocks.reserve(pairs.size() * 2 + 8);
-    // the scene root's block and the blocks of its (up to four) grandchildren
-    // come first, blocks 0-4: the top four levels of the tree in 320 B (the
-    // MTSG_LDS_TOP variant stages them in LDS)
-    std::unordered_map<uint32_t, uint32_t> preBlock;
-    auto reserveBlock = [&](uint32_t pair) {
-        preBlock[pair] = (uint32_t)(blocks.size() / 4);
-        blocks.resize(blocks.size() + 4, make_uint4(0, 0, 0, 0));
-    };
-    if (!(root.x & 0x80000000u)) {
-        reserveBlock(root.x >> 2);
-        const uint4 pr = pairs[root.x >> 2];
-        for (const uint2 c : {make_uint2(pr.x, pr.y), make_uint2(pr.z, pr.w)}) {
-            if (c.x & 0x80000000u) continue;
-            const uint4 gp = pairs[c.x >> 2];
-            for (const uint2 g : {make_uint2(gp.x, gp.y), make_uint2(gp.z, gp.w)})
-                if (!(g.x & 0x80000000u)) reserveBlock(g.x >> 2);
-        }
-    }
-    std::function<uint2(uint2, bool, uint32_t)> conv2 = [&](uint2 w, bool root, uint32_t slot) -> uint2 {
-        if (w.x & 0x80000000u) return w;                       // leaf: unchanged
-        const uint4 pr = pairs[w.x >> 2];
-        const uint2 L = make_uint2(pr.x, pr.y), R = make_uint2(pr.z, pr.w);
-        if (root) {
-            uint32_t b;
-            const auto pre = preBlock.find(w.x >> 2);
-            if (pre != preBlock.end()) {
-                b = pre->second;
-            } else {
-                b = (uint32_t)(blocks.size() / 4);
-                blocks.resize(blocks.size() + 4, make_uint4(0, 0, 0, 0));
-            }
-            const uint2 nL = conv2(L, false, 4 * b + 1);
-            const uint2 nR = conv2(R, false, 4 * b + 2);
-            blocks[4 * b] = make_uint4(nL.x, nL.y, nR.x, nR.y);
-            return make_uint2((w.x & 3u) | (b << 3), w.y);
-        }
-        // pair-only node: its children are block roots (or leaves)
-        const uint2 nL = conv2(L, true, 0), nR = conv2(R, true, 0);
-        blocks[slot] = make_uint4(nL.x, nL.y, nR.x, nR.y);
-        return make_uint2((w.x & 3u) | 4u | (slot << 3), w.y);
-    };
-    const uint2 root2 = conv2(root, true, 0);
-    for (auto &gr : groupRoots) gr = conv2(gr, true, 0);
-    blocks.resize(blocks.size() + 4, make_uint4(0, 0, 0, 0));   // slack for the 3-slot fetch of the last slot
-    if (blocks.size() < 20) blocks.resize(20, make_uint4(0, 0, 0, 0));   // blocks 0-4 are always readable
-    if (blocks.size() >= (1u << 29)) { g_err = "kd-tree too large for the two-level layout"; return fail(MTSG_ERR_INVALID); }
-    if (triL.empty()) triL.resize(3, make_float4(0, 0, 0, 0));
-    uint4 *dblocks; float4 *dtriL; float4 *dvpos, *dvnrm, *dshrec; uint4 *dtidx;
+    static_assert(sizeof(KdU4) == sizeof(uint4) && sizeof(KdF4) == sizeof(float4), "kd_layout.h arrays upload as uint4 / float4");
+    const std::vector<KdU2> &groupRoots = lay.groupRoots;
+    const uint2 root2 = make_uint2(lay.root2.x, lay.root2.y);
+    uint4 *dblocks, *dblocksRS; float4 *dtriL; float4 *dvpos, *dvnrm, *dshrec; uint4 *dtidx;
     mtsg_rect *rects; mtsg_shape *shapes; mtsg_bsdf *bsdfs; mtsg_emitter *emitters; float *ecdf, *etcdf;
-    if ((rc = up(triL.data(), triL.size(), &dtriL)) ||
-        (rc = up(blocks.data(), blocks.size(), &dblocks)) ||
+    if ((rc = up(reinterpret_cast<const float4 *>(lay.triL.data()), lay.triL.size(), &dtriL)) ||
+        (rc = up(reinterpret_cast<const uint4 *>(lay.blocks.data()), lay.blocks.size(), &dblocks)) ||
+        (rc = up(reinterpret_cast<const uint4 *>(lay.blocksRS.data()), lay.blocksRS.size(), &dblocksRS)) ||
         (rc = up(vpos.data(), vpos.size(), &dvpos)) || (rc = up(vnrm.data(), vnrm.size(), &dvnrm)) ||
         (rc = up(tidx.data(), tidx.size(), &dtidx)) ||
         (rc = up(shrec.data(), shrec.size(), &dshrec)) ||
@@ -1401,6 +1292,8 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
         (rc = up(d->emitter_tri_cdf, d->n_emitter_tri_cdf, &etcdf)))
         return fail(rc);
     ds.blocks = dblocks; ds.root2 = root2;
+    s->blocksRS = dblocksRS;   // null: no leaf references a rectangle, or the scene does not take the setup mode
+    s->root2RS = make_uint2(lay.root2RS.x, lay.root2RS.y);
     ds.triL = dtriL; ds.vpos = dvpos; ds.vnrm = dvnrm;
     int constantEmitter = -1;   // index of the scene's constant environment emitter
     {
@@ -1510,7 +1403,7 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
                 o[r] = make_float4(L[4 * r], L[4 * r + 1], L[4 * r + 2], L[4 * r + 3]);
                 o[3 + r] = make_float4(W[4 * r], W[4 * r + 1], W[4 * r + 2], W[4 * r + 3]);
             }
-            const uint2 gr = groupRoots[I.group];
+            const KdU2 gr = groupRoots[I.group];
             float r0, r1;
             memcpy(&r0, &gr.x, 4);
             memcpy(&r1, &gr.y, 4);
@@ -1662,14 +1555,6 @@ int mtsg_scene_create(const mtsg_scene_desc *d, int device, mtsg_scene **out) {
     ds.n_emitters = d->n_emitters;
     ds.n_tri = d->n_triangles;
     ds.n_rect = d->n_rects;
-    // the setup mode names rectangle r by the tie key n_triangles + r, its
-    // TriAccel index in the leaf records: hold the description to that
-    s->rectSetupOk = MTSG_RECT_SETUP && d->n_rects <= RECT_SETUP_CAP;
-    for (uint32_t r = 0; r < d->n_rects && s->rectSetupOk; ++r) {
-        const mtsg_triaccel &ta = d->triaccel[d->n_triangles + r];
-        s->rectSetupOk = ta.k == MTSG_TRIACCEL_SHAPE && ta.prim_index == r && ta.shape_index < d->n_shapes &&
-                         d->shapes[ta.shape_index].type == MTSG_SHAPE_RECT;
-    }
     ds.n_bsdfs = d->n_bsdfs;
     for (int k = 0; k < 3; ++k) { ds.bmin[k] = d->aabb_min[k]; ds.bmax[k] = d->aabb_max[k]; }
     DevCamera &c = s->cam;
@@ -1865,6 +1750,10 @@ int mtsg_set_option(mtsg_scene *s, int32_t key, int64_t value) {
         case MTSG_OPT_RAY_PRESETUP:
             if (value < 0 || value > 1) { g_err = "MTSG_OPT_RAY_PRESETUP: 0 (rectangles tested in the traversal's refill) or 1 (where the rays are made)"; return MTSG_ERR_INVALID; }
             s->rayPresetupOpt = value != 0;
+            return MTSG_OK;
+        case MTSG_OPT_LEAF_FILTER:
+            if (value < 0 || value > 1) { g_err = "MTSG_OPT_LEAF_FILTER: 0 (the setup mode steps over rectangle records) or 1 (its leaves hold none)"; return MTSG_ERR_INVALID; }
+            s->leafFilterOpt = value != 0;
             return MTSG_OK;
         default:
             g_err = "unknown option key " + std::to_string(key);

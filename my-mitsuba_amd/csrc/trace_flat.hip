@@ -48,7 +48,18 @@ static void launch_flat(const FlatTraceLaunch &a) {
     // (a.rectSetup false): in the leaves.  The COUNT pass follows the timed kernel.
     // a.pre: the rays carry pre-records, the refill runs no rectangle loop
     // (k_trace_s_pre; the launcher sets it only with a.rectSetup and without a.knobs)
-    if (a.pre && a.rectSetup && !a.knobs) {
+    // a.leafFilter: those setup-mode kernels, timed (not COUNT: every counter
+    // describes the walk over Mitsuba's leaves), read the leaf words of
+    // blocksRS, which hold no rectangle records; k_tie below keeps a.S
+    if (!COUNT && a.leafFilter && a.blocksRS && a.rectSetup && !a.knobs) {
+        DevScene S = *a.S;
+        S.blocks = a.blocksRS;
+        S.root2 = a.root2RS;
+        if (a.pre && a.refill32) hipLaunchKernelGGL((k_trace_s_pre<COUNT, 32>), a.grid, blk, 0, a.stream, S, *a.P, a.cIn, a.sIn, a.n, a.wt);
+        else if (a.pre) hipLaunchKernelGGL((k_trace_s_pre<COUNT, 16>), a.grid, blk, 0, a.stream, S, *a.P, a.cIn, a.sIn, a.n, a.wt);
+        else if (a.refill32) hipLaunchKernelGGL((k_trace_s<COUNT, 32>), a.grid, blk, 0, a.stream, S, *a.P, a.cIn, a.sIn, a.n, a.wt);
+        else hipLaunchKernelGGL((k_trace_s<COUNT, 16>), a.grid, blk, 0, a.stream, S, *a.P, a.cIn, a.sIn, a.n, a.wt);
+    } else if (a.pre && a.rectSetup && !a.knobs) {
         if (a.refill32) hipLaunchKernelGGL((k_trace_s_pre<COUNT, 32>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
         else hipLaunchKernelGGL((k_trace_s_pre<COUNT, 16>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);
     } else if (a.knobs && !COUNT) hipLaunchKernelGGL((k_trace_s<false, 16, false, true>), a.grid, blk, 0, a.stream, *a.S, *a.P, a.cIn, a.sIn, a.n, a.wt);

@@ -37,7 +37,8 @@ MTSG_OPT_RAY_ORDER = 6
 MTSG_OPT_CAMERA_DIFFS = 7
 MTSG_OPT_RECT_SETUP = 8
 MTSG_OPT_RAY_PRESETUP = 9
-MTSG_RECT_SETUP_CAP = 2   # most rectangles of a flat scene for MTSG_OPT_RECT_SETUP 1 to apply
+MTSG_OPT_LEAF_FILTER = 10
+MTSG_RECT_SETUP_CAP = 8  # most rectangles of a flat scene for MTSG_OPT_RECT_SETUP 1 to apply
 # mtsg_render_params.integrator
 MTSG_INTEGRATOR_PATH = 0
 MTSG_INTEGRATOR_PATH2_OM = 1
