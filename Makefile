@@ -23,7 +23,7 @@ ORACLE      := oracle/liboracle.so
 ORACLE_FAST := oracle/liboracle_fast.so
 
 .PHONY: all host device oracle clean
-all: host device oracle $(PATH_LIB) $(CLI) scenes/sky512.pfm tools/math_probe tools/math_bench tools/div_probe tools/check_glibc_mathf tools/check_env_guide tools/check_multichannel_host tools/check_render_plan tools/check_kd_layout
+all: host device oracle $(PATH_LIB) $(CLI) scenes/sky512.pfm tools/math_probe tools/math_bench tools/div_probe tools/check_glibc_mathf tools/check_env_guide tools/check_multichannel_host tools/check_render_plan tools/check_kd_layout tools/check_adaptive_plan
 host: $(HOST_LIB)
 device: $(DEV_LIB)
 oracle: $(ORACLE) $(ORACLE_FAST)
@@ -50,7 +50,7 @@ DEV_FLAGS := -O3 -std=c++17 -fPIC -Wall -ffp-contract=off -fno-slp-vectorize -mu
 # -0.6%; the two-level kernel in mtsg.hip loses 3% under it: DESIGN §3)
 DEV_FLAT_FLAGS ?= -mllvm -amdgpu-sched-strategy=max-memory-clause
 DEV_OBJ   ?= build/dev
-DEV_OBJS  := $(DEV_OBJ)/mtsg.o $(DEV_OBJ)/trace_flat.o $(DEV_OBJ)/fields.o $(DEV_OBJ)/direct.o $(DEV_OBJ)/direct2.o $(DEV_OBJ)/kdbuild.o $(foreach k,0 1 2 3 4,$(DEV_OBJ)/smp_$(k).o $(DEV_OBJ)/smp2_$(k).o)
+DEV_OBJS  := $(DEV_OBJ)/mtsg.o $(DEV_OBJ)/trace_flat.o $(DEV_OBJ)/fields.o $(DEV_OBJ)/direct.o $(DEV_OBJ)/direct2.o $(DEV_OBJ)/adaptive.o $(DEV_OBJ)/kdbuild.o $(foreach k,0 1 2 3 4,$(DEV_OBJ)/smp_$(k).o $(DEV_OBJ)/smp2_$(k).o)
 $(DEV_OBJ)/mtsg.o: $(PKG)/csrc/mtsg.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
@@ -69,6 +69,10 @@ $(DEV_OBJ)/direct.o: $(PKG)/csrc/direct.hip $(DEV_HDR)
 $(DEV_OBJ)/direct2.o: $(PKG)/csrc/direct.hip $(DEV_HDR)
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -DMTSG_TU_EXT2 -c -o $@ $<
+# the adaptive integrator's camera and splat kernels (adaptive.hip)
+$(DEV_OBJ)/adaptive.o: $(PKG)/csrc/adaptive.hip $(DEV_HDR)
+	@mkdir -p $(DEV_OBJ)
+	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
 $(DEV_OBJ)/kdbuild.o: $(PKG)/csrc/kdbuild.hip include/mtsg.h
 	@mkdir -p $(DEV_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(DEV_FLAGS) $(DEV_EXTRA) -c -o $@ $<
@@ -129,6 +133,11 @@ tools/check_multichannel_host: tools/check_multichannel_host.cpp $(HOST_SRC) $(H
 # the batch plan of a render call (csrc/render_plan.h: host-only integer
 # arithmetic) over a sweep of shapes, under ASan + UBSan (CPU only)
 tools/check_render_plan: tools/check_render_plan.cpp $(PKG)/csrc/render_plan.h
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -o $@ $<
+
+# the round bookkeeping of an adaptive render (csrc/adaptive_plan.h: host-only
+# integer arithmetic) over a sweep of shapes, under ASan + UBSan (CPU only)
+tools/check_adaptive_plan: tools/check_adaptive_plan.cpp $(PKG)/csrc/adaptive_plan.h $(PKG)/csrc/render_plan.h
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -o $@ $<
 
 # the device kd-tree layout and its filtered leaf addressing (csrc/kd_layout.h:

@@ -729,6 +729,12 @@ int  mtsg_set_finish_paths(mtsg_scene *scene, uint32_t paths);
  *                             those records in the scene's own leaves (A/B
  *                             tests).  Counting renders (MTSG_FLAG_COUNT) always
  *                             walk the scene's own leaves.
+ *   MTSG_OPT_ADAPTIVE_ROUND   adaptive renders: the samples per pixel of every
+ *                             round after the first, which covers base_count
+ *                             (1..65536; 0, the default, = base_count).  The
+ *                             per-pixel counts do not depend on it; the film's
+ *                             sums are regrouped, so it agrees to rounding, not
+ *                             bit for bit.
  * Unknown keys and values out of range return MTSG_ERR_INVALID. */
 /* the most rectangles a flat scene may hold for MTSG_OPT_RECT_SETUP 1 to apply */
 #define MTSG_RECT_SETUP_CAP 8u
@@ -742,7 +748,8 @@ enum {
     MTSG_OPT_CAMERA_DIFFS = 7,
     MTSG_OPT_RECT_SETUP = 8,
     MTSG_OPT_RAY_PRESETUP = 9,
-    MTSG_OPT_LEAF_FILTER = 10
+    MTSG_OPT_LEAF_FILTER = 10,
+    MTSG_OPT_ADAPTIVE_ROUND = 11
 };
 int  mtsg_set_option(mtsg_scene *scene, int32_t key, int64_t value);
 
@@ -1006,6 +1013,69 @@ typedef struct mtsg_direct_desc {
  * with MTSG_INTEGRATOR_DIRECT or MTSG_INTEGRATOR_AO and no descriptor returns
  * MTSG_ERR_INVALID; `path` renders ignore it. */
 int  mtsg_scene_set_direct(mtsg_scene *scene, const mtsg_direct_desc *desc);
+
+/* ---- adaptive integrator ------------------------------------------------------
+ * Mitsuba's `adaptive` meta-integrator (src/integrators/misc/adaptive.cpp:68-285)
+ * around a `path` child: a pixel is sampled until a Z-test on its luminance is
+ * satisfied or a cap is reached.  With N = base_count, a pixel takes samples
+ * count = 1, 2, ...; a sample that ImageBlock::put rejects counts with
+ * luminance 0 (adaptive.cpp:235-240); Knuth's running mean / meanSqr in float
+ * (:246-248); the pixel stops when count >= max_sample_factor * N (:250), or
+ * else, from count >= N on, when
+ *   sqrt((meanSqr / (count - 1)) / count) * quantile <= max_error * max(mean, 0.01 * averageLuminance)
+ * (:252-269).  What the pixel added to the block is scaled by 1 / count
+ * (:273-283), so the block is  sum_pixels (1 / n_p) sum_{s < n_p} w * v.
+ * averageLuminance is the mean luminance of 10000 `path` samples at uniformly
+ * random positions of the full film, without ray differentials (preprocess,
+ * :125-159); their sample ids follow the film's, so no pixel shares them.
+ * Sample s of pixel p is sample s of the plain `path` render of the scene with
+ * spp = cap = max(1, max_sample_factor * N), bit for bit; the camera ray
+ * differentials are scaled by 1 / sqrt(N) (:183-184,230).
+ * The parameters travel beside the scene descriptor, whose layout they leave
+ * alone; mtsh_scene_adaptive fills them. */
+typedef struct mtsg_adaptive_desc {
+    float    max_error;           /* maxError (adaptive.cpp:72), >= 0              */
+    float    quantile;            /* m_quantile (adaptive.cpp:161-162)             */
+    int32_t  max_sample_factor;   /* maxSampleFactor (adaptive.cpp:77), >= 0: the  */
+                                  /* reference's negative "infinity" is refused    */
+    uint32_t base_count;          /* the sampler's sampleCount N (>= 8, :176-178)  */
+} mtsg_adaptive_desc;
+
+/* Set (or, desc == NULL, remove) the adaptive descriptor of a scene handle.
+ * While one is set, mtsg_render and mtsg_render_device with
+ * MTSG_INTEGRATOR_PATH render adaptively: params.spp must equal base_count
+ * and the sampler must be the independent one.  A tile share (tile_stride /
+ * tile_offset, or mtsg_set_tile_list) renders too: a pixel belongs to one
+ * tile, every share computes the same pre-pass value, and the shares' blocks
+ * sum to the whole rectangle's, as the plain film's do; the multi-GPU path
+ * job and mtsg-render run adaptive scenes that way.  The entries whose output
+ * has no fixed shape under a per-pixel sample count, or whose windows are
+ * numbered by a tile list that shrinks from round to round, return
+ * MTSG_ERR_INVALID with a message instead: mtsg_render_samples,
+ * mtsg_render_device_tiles and the *_multi entries; so does a render with
+ * another integrator than MTSG_INTEGRATOR_PATH.  mtsg_cancel ends the render
+ * between rounds, batches and bounces; the tile callback fires when a tile's
+ * last pixel has stopped. */
+int  mtsg_scene_set_adaptive(mtsg_scene *scene, const mtsg_adaptive_desc *desc);
+
+/* The last adaptive render of the handle (AdaptiveIntegrator's log line,
+ * adaptive.cpp:163-164, and its per-pixel sampleCount, :241): the pre-pass
+ * average luminance (and the sample variance of its 10000 luminances, in
+ * double then float: a diagnostic of how well it is known), the quantile,
+ * the samples taken over all pixels (the pre-pass's 10000 not included), the
+ * rounds the render took, and, counts != NULL, the sample count of
+ * every pixel of the rendered rectangle, row-major, capacity >= tile_w *
+ * tile_h entries (else MTSG_ERR_INVALID).  MTSG_ERR_INVALID before the first
+ * such render. */
+typedef struct mtsg_adaptive_result {
+    float    average_luminance;
+    float    quantile;
+    uint64_t total_samples;
+    int32_t  width, height;       /* the rendered rectangle                        */
+    uint32_t rounds;              /* rounds the render took                        */
+    float    luminance_variance;  /* sample variance of the pre-pass luminances    */
+} mtsg_adaptive_result;
+int  mtsg_adaptive_info(mtsg_scene *scene, mtsg_adaptive_result *out, uint32_t *counts, size_t capacity);
 
 void mtsg_scene_destroy(mtsg_scene *scene);
 

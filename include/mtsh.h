@@ -190,7 +190,12 @@ int32_t mtsh_scene_set_integrator(mtsh_builder *b, const char *plugin, const mts
  * `field`, field.cpp:69-110; -> the child's position, or -1), then the parent
  * is set, which takes the children added so far (props: multichannel's own,
  * it reads none).  mtsh_scene_set_integrator("multichannel") does the same as
- * the second call.  The film's pixelFormat must list one entry per child. */
+ * the second call.  The film's pixelFormat must list one entry per child.
+ * The `adaptive` integrator (adaptive.cpp:68-116) takes its one `path` child
+ * the same way: mtsh_scene_add_integrator_child("path"), then
+ * mtsh_scene_set_integrator("adaptive") with maxError, pValue and
+ * maxSampleFactor (not negative: a bound is required).  It needs the
+ * independent sampler and a sampleCount of at least 8. */
 int32_t mtsh_scene_add_integrator_child(mtsh_builder *b, const char *plugin, const mtsh_prop *props, int32_t n_props);
 int32_t mtsh_scene_set_multichannel(mtsh_builder *b, const mtsh_prop *props, int32_t n_props);
 /* The Scene's own Properties (Scene::Scene(props), scene.cpp:47-83; a
@@ -247,6 +252,14 @@ const mtsg_aov_desc *mtsh_scene_aov(const mtsh_scene *scene);
  * `rayLength` is half the radius of the scene's bounding sphere (ao.cpp:72-82;
  * the kd-tree AABB expanded by the sensor position, scene.cpp:412-440). */
 int mtsh_scene_direct(const mtsh_scene *scene, mtsg_direct_desc *out);
+
+/* The adaptive descriptor of the scene (mtsg.h, for mtsg_scene_set_adaptive):
+ * returns 1 and fills *out (may be NULL) when the scene's integrator is
+ * `adaptive` (around a `path` child, whose properties mtsh_scene_render_params
+ * gives), else 0.  AdaptiveIntegrator(props) and preprocess, adaptive.cpp:70-81,
+ * 161-162: quantile = (float) of the standard normal quantile at 1 - pValue / 2,
+ * base_count = the sampler's sampleCount. */
+int mtsh_scene_adaptive(const mtsh_scene *scene, mtsg_adaptive_desc *out);
 
 /* The film's pixelFormat entries and channel names (hdrfilm.cpp:216-295).
  * formats (may be NULL) receives up to capacity MTSH_FORMAT_* ids, the count

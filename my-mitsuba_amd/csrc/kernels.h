@@ -333,6 +333,36 @@ void launch_direct_resolve(const DirectLaunch &a);   // after the fan's trace la
 void launch_direct_shade_ext2(const DirectLaunch &a);     // the same for DirectLaunch::ext2 scenes (direct.hip
 void launch_direct_resolve_ext2(const DirectLaunch &a);   // compiled with MTSG_TU_EXT2, a unit of its own)
 
+// adaptive integrator (adaptive.hip, its own translation unit): the per-pixel
+// state of a render, indexed by deal key * 256 + the pixel's position in its
+// tile (tile_pix), `stride` entries per plane.  A pixel that goes on past a
+// batch parks its K x K x CH filter window in `win` (plane (r * K + c) * CH + h).
+struct DevAdaptive {
+    uint32_t *status;       // samples taken so far; bit 31: the pixel has stopped
+    float *mean, *meanSqr;  // Knuth's running statistics (adaptive.cpp:246-248)
+    float *win;
+    uint32_t *tileActive;   // per deal key: the tile still holds an active pixel (written by every splat)
+    size_t stride;
+    float maxError, quantile, avgLum;
+    uint32_t baseCount;     // N: the Z-test starts there; the differentials' 1 / sqrt(N)
+    uint32_t limit;         // maxSampleFactor * N (0: one sample)
+    int prepass;            // the camera draws film positions (adaptive.cpp:142-144) and leaves the differentials out
+};
+constexpr uint32_t ADAPTIVE_DONE = 0x80000000u;
+struct AdaptiveLaunch {
+    hipStream_t stream;
+    const DevScene *S;
+    const DevCamera *C;
+    const DevIntegrator *I;
+    const DevBatch *B;
+    const DevPaths *P;
+    const DevAdaptive *A;
+    float *film;
+    int blockW, blockH;
+};
+void launch_adaptive_camera(const AdaptiveLaunch &a);   // k_camera / k_camera_lens with the per-pixel mask
+void launch_adaptive_splat(const AdaptiveLaunch &a);    // statistics, stop test, 1 / count, film
+
 }  // namespace mtsg
 
 using namespace mtsg;

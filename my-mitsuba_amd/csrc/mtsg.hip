@@ -38,6 +38,7 @@
 
 #include "kernels.h"
 #include "render_plan.h"
+#include "adaptive_plan.h"
 #include "kd_layout.h"
 
 // the default of MTSG_OPT_RAY_PRESETUP.  0: measured on C3, the producers' tests
@@ -203,6 +204,15 @@ struct mtsg_scene {
     DevDirect fan{};
     std::vector<void *> fanAllocs;
     size_t fanClosest = 0, fanShadow = 0;   // BSDF / shadow rays the buffers hold
+    // adaptive integrator (mtsg_scene_set_adaptive; adaptive.hip): the
+    // descriptor, the size of the rounds after the first (MTSG_OPT_ADAPTIVE_ROUND,
+    // 0: the base count), and what the last such render leaves for mtsg_adaptive_info
+    bool adaptiveOn = false;
+    mtsg_adaptive_desc adaptive{};
+    uint32_t adaptiveRound = 0;
+    bool adaptiveHave = false;
+    mtsg_adaptive_result adaptiveResult{};
+    std::vector<uint32_t> adaptiveCounts;
 };
 
 namespace {
@@ -647,6 +657,10 @@ struct RenderRun {
     // k_shade write each ray's pre-record and the trace launches read it.  Not
     // the multichannel, direct / ao and myPath2_OM routes: their rays carry none.
     bool pre = false;
+    // adaptive (adaptive.hip): its camera in place of k_camera, its splat in
+    // place of k_splat (none in the pre-pass), rounds in place of the plan
+    bool adaptive = false;
+    DevAdaptive adv{};
     int blockW = 0, blockH = 0, maxBounces = 0;
     struct Lane {
         DevBatch B;
@@ -678,6 +692,9 @@ struct RenderRun {
     DirectLaunch direct_args(uint32_t l) const {
         return DirectLaunch{s->lstream[l], &s->ds, &I, &lane[l].B, &s->LP[l], &s->fan, s->cam.has_alpha, (s->ds.has_env & 1) != 0, s->extBsdfs,
                             s->shadeGeneric ? (int)MATS_ALL : s->mats, s->emitterSet == EM_ALL, s->ext2};
+    }
+    AdaptiveLaunch adaptive_args(uint32_t l) const {
+        return AdaptiveLaunch{s->lstream[l], &s->ds, &s->cam, &I, &lane[l].B, &s->LP[l], &adv, film, blockW, blockH};
     }
     FieldsLaunch fields(uint32_t l) const {
         return FieldsLaunch{s->lstream[l], &s->ds, &s->cam, &I, &lane[l].B, &s->LP[l], &s->aov, film, blockW, blockH, win};
@@ -734,7 +751,8 @@ struct RenderRun {
             P.pre = pre ? P.preBuf : nullptr;
             timed_launch(s, K_CAMERA, st, [&]() {
                 const dim3 g((L.B.nslots + BLOCK - 1) / BLOCK);
-                if (s->cam.lens && pre) hipLaunchKernelGGL(k_camera_lens<true>, g, dim3(BLOCK), 0, st, s->ds, s->cam, I, L.B, P);
+                if (adaptive) launch_adaptive_camera(adaptive_args(l));
+                else if (s->cam.lens && pre) hipLaunchKernelGGL(k_camera_lens<true>, g, dim3(BLOCK), 0, st, s->ds, s->cam, I, L.B, P);
                 else if (s->cam.lens) hipLaunchKernelGGL(k_camera_lens<false>, g, dim3(BLOCK), 0, st, s->ds, s->cam, I, L.B, P);
                 else if (pre) hipLaunchKernelGGL(k_camera<true>, g, dim3(BLOCK), 0, st, s->ds, s->cam, I, L.B, P);
                 else hipLaunchKernelGGL(k_camera<false>, g, dim3(BLOCK), 0, st, s->ds, s->cam, I, L.B, P);
@@ -823,10 +841,11 @@ struct RenderRun {
             HIP_TRY(hipEventRecord(L.cntEv[L.last & 1], st));
         }
         timed_launch(s, K_SPLAT, st, [&]() {
-            if (multi) launch_splat_multi(fields(l));
+            if (adaptive) { if (!adv.prepass) launch_adaptive_splat(adaptive_args(l)); }
+            else if (multi) launch_splat_multi(fields(l));
             else launch_splat(s, I, L.B, P, film, blockW, blockH, win, st);
         });
-        s->stats.samples += (uint64_t)L.B.nslots;
+        if (!adaptive) s->stats.samples += (uint64_t)L.B.nslots;
         return MTSG_OK;
     }
 
@@ -866,7 +885,7 @@ struct RenderRun {
                 return MTSG_ERR_INVALID;
             }
         }
-        if (s->tileFn) {
+        if (s->tileFn && !adaptive) {   // (adaptive: a tile is complete when its last pixel stops, run_adaptive)
             // the tiles whose last samples this batch splatted are complete
             for (uint32_t l = 0; l < nb; ++l) {
                 HIP_TRY(hipStreamSynchronize(s->lstream[l]));
@@ -956,22 +975,132 @@ struct RenderRun {
                 L.start = (int)l * s->stagger;
             }
             int rc;
-            for (int gb = 0;; ++gb) {
-                // cancel() between bounces (the whole frame is usually one batch)
-                if (s->cancel.load()) { g_err = "cancelled"; return MTSG_ERR_CANCELLED; }
-                for (uint32_t l = 0; l < nb; ++l)
-                    if (lane[l].open && gb >= lane[l].start && (rc = issue_bounce(l, gb - lane[l].start)) != MTSG_OK) return rc;
-                bool any = false;
-                for (uint32_t l = 0; l < nb; ++l) {
-                    if ((rc = check_empty(l, gb - lane[l].start)) != MTSG_OK) return rc;
-                    any |= lane[l].open;
-                }
-                if (!any) break;
-            }
-            for (uint32_t l = 0; l < nb; ++l)
-                if ((rc = close_batch(l)) != MTSG_OK) return rc;
-            if ((rc = collect_batches(nb)) != MTSG_OK) return rc;
+            if ((rc = run_bounces(nb)) != MTSG_OK) return rc;
         }
+        return MTSG_OK;
+    }
+
+    // the nb batches in lane[0..nb) from their camera rays to their splat
+    int run_bounces(uint32_t nb) {
+        int rc;
+        for (int gb = 0;; ++gb) {
+            // cancel() between bounces (the whole frame is usually one batch)
+            if (s->cancel.load()) { g_err = "cancelled"; return MTSG_ERR_CANCELLED; }
+            for (uint32_t l = 0; l < nb; ++l)
+                if (lane[l].open && gb >= lane[l].start && (rc = issue_bounce(l, gb - lane[l].start)) != MTSG_OK) return rc;
+            bool any = false;
+            for (uint32_t l = 0; l < nb; ++l) {
+                if ((rc = check_empty(l, gb - lane[l].start)) != MTSG_OK) return rc;
+                any |= lane[l].open;
+            }
+            if (!any) break;
+        }
+        for (uint32_t l = 0; l < nb; ++l)
+            if ((rc = close_batch(l)) != MTSG_OK) return rc;
+        return collect_batches(nb);
+    }
+
+    // one batch on lane 0
+    int run_single(const DevBatch &B) {
+        Lane &L = lane[0];
+        L.B = B;
+        L.last = -1;
+        L.open = true;
+        L.finished = false;
+        L.start = 0;
+        return run_bounces(1);
+    }
+
+    // An adaptive render (adaptive.hip, adaptive_plan.h): the pre-pass, then
+    // rounds over the tiles that still hold an active pixel.  keys: the call's
+    // deal keys; keysDev: room for them on the device; maxPaths: the memory fit;
+    // Ipre / preB: the integrator constants and the batch of the pre-pass strip.
+    int run_adaptive(std::vector<int32_t> keys, int32_t *keysDev, uint32_t maxPaths, const DevIntegrator &Ipre, const DevBatch &preB,
+                     uint32_t later) {
+        int rc;
+        mtsg_adaptive_result &res = s->adaptiveResult;
+        const DevIntegrator Irounds = I;
+        // pre-pass (adaptive.cpp:125-159): the strip's luminances, summed in
+        // float in sample order on the host, so every GPU of a split render
+        // holds the same value
+        {
+            I = Ipre;
+            adv.prepass = 1;
+            rc = run_single(preB);
+            I = Irounds;
+            adv.prepass = 0;
+            if (rc != MTSG_OK) return rc;
+            std::vector<float4> L(preB.nslots);
+            HIP_TRY(hipMemcpyAsync(L.data(), s->LP[0].L, L.size() * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            std::vector<float> lum(ADAPTIVE_PREPASS_SAMPLES, 0.0f);
+            for (uint32_t slot = 0; slot < preB.nslots; ++slot) {
+                int lx, ly;
+                tile_pix(slot & (TILE * TILE - 1), lx, ly);
+                const uint32_t i = (((slot >> 8) * TILE) + (uint32_t)ly) * TILE + (uint32_t)lx;
+                if (i < ADAPTIVE_PREPASS_SAMPLES) lum[i] = L[slot].x * 0.212671f + L[slot].y * 0.715160f + L[slot].z * 0.072169f;
+            }
+            float sum = 0.0f;
+            for (float v : lum) sum += v;
+            adv.avgLum = sum / (float)ADAPTIVE_PREPASS_SAMPLES;
+            res.average_luminance = adv.avgLum;
+            double m = 0, q = 0;
+            for (float v : lum) m += v;
+            m /= ADAPTIVE_PREPASS_SAMPLES;
+            for (float v : lum) q += (v - m) * (v - m);
+            res.luminance_variance = (float)(q / (ADAPTIVE_PREPASS_SAMPLES - 1));
+        }
+        std::vector<uint32_t> active(plan.allTiles, 0u);
+        std::vector<int32_t> finished;
+        const uint32_t N = adv.baseCount, cap = I.spp;
+        for (uint32_t r = 0; !keys.empty(); ++r) {
+            uint32_t s0, ns;
+            if (!adaptive_round(N, cap, later, r, s0, ns)) { g_err = "adaptive: pixels left active past the cap"; return MTSG_ERR_DEVICE; }
+            // cancel() between rounds, as between batches
+            if (s->cancel.load()) { g_err = "cancelled"; return MTSG_ERR_CANCELLED; }
+            HIP_TRY(hipMemcpyAsync(keysDev, keys.data(), keys.size() * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+            const RenderPlan rp = adaptive_round_plan(p->tile_w, p->tile_h, (uint32_t)keys.size(), s0, ns, maxPaths);
+            for (const PlanBatch &b : rp.batches) {
+                if (s->cancel.load()) { g_err = "cancelled"; return MTSG_ERR_CANCELLED; }
+                DevBatch B = dev_batch(b);
+                B.tstride = 1;
+                B.toffset = 0;
+                B.keys = keysDev;
+                if (B.nslots > s->capacity) { g_err = "adaptive: a round's batch exceeds the path state"; return MTSG_ERR_DEVICE; }
+                if ((rc = run_single(B)) != MTSG_OK) return rc;
+            }
+            // the tiles whose last pixel stopped leave the list
+            HIP_TRY(hipMemcpyAsync(active.data(), adv.tileActive, active.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            adaptive_compact(keys, active, finished);
+            res.rounds = r + 1;
+            if (s->tileFn)
+                for (int32_t key : finished) {
+                    int x, y, w, h;
+                    tile_rect(key, lane[0].B, x, y, w, h);
+                    s->tileFn(s->tileUser, key, p->tile_x + x, p->tile_y + y, w, h);
+                }
+        }
+        // the per-pixel counts of the rectangle, row-major
+        std::vector<uint32_t> status((size_t)plan.allTiles * TILE * TILE);
+        HIP_TRY(hipMemcpy(status.data(), adv.status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        s->adaptiveCounts.assign((size_t)p->tile_w * p->tile_h, 0u);
+        uint64_t total = 0;
+        for (uint32_t key = 0; key < plan.allTiles; ++key) {
+            int tx, ty;
+            tile_of_key((int)key, (int)plan.tilesX, tx, ty, PLAN_DEAL_SKEW);
+            for (uint32_t pix = 0; pix < (uint32_t)(TILE * TILE); ++pix) {
+                int lx, ly;
+                tile_pix(pix, lx, ly);
+                const int x = tx * TILE + lx, y = ty * TILE + ly;
+                if (x >= p->tile_w || y >= p->tile_h) continue;
+                const uint32_t c = status[(size_t)key * TILE * TILE + pix] & ~ADAPTIVE_DONE;
+                s->adaptiveCounts[(size_t)y * p->tile_w + x] = c;
+                total += c;
+            }
+        }
+        res.total_samples = total;
+        s->stats.samples = total;
         return MTSG_OK;
     }
 
@@ -996,7 +1125,7 @@ struct RenderRun {
         if (result != MTSG_OK) return result;
         mtsg_stats &st = s->stats;
         // samples actually inside the rectangle (all tiles of this call)
-        if (plan.tstride == 1 && s->tileKeys.empty()) st.samples = (uint64_t)p->tile_w * p->tile_h * p->spp;
+        if (plan.tstride == 1 && s->tileKeys.empty() && !adaptive) st.samples = (uint64_t)p->tile_w * p->tile_h * p->spp;
         if (s->flags & MTSG_FLAG_TIMING) {
             // in the order of K_CAMERA .. K_SORT
             double *const sums[] = {&st.ms_camera, &st.ms_trace_closest, &st.ms_trace_shadow, &st.ms_shade, &st.ms_splat, &st.ms_finish, &st.ms_sort};
@@ -1038,10 +1167,135 @@ struct RenderRun {
     }
 };
 
+// A render call on a handle with an adaptive descriptor (mtsg.h
+// mtsg_scene_set_adaptive): its checks, the per-pixel state, then
+// RenderRun::run_adaptive.  The state is allocated before the memory fit, so
+// the fit sees what is left, and freed when the call returns.
+int render_adaptive(mtsg_scene *s, const mtsg_render_params *p, float *film, int win, bool multi) {
+    const mtsg_adaptive_desc &d = s->adaptive;
+    if (p->integrator != MTSG_INTEGRATOR_PATH) { g_err = "adaptive: the child integrator must be `path`"; return MTSG_ERR_INVALID; }
+    if (multi || s->aovOn) { g_err = "adaptive: not inside or around `multichannel`"; return MTSG_ERR_INVALID; }
+    if (s->dumpL) { g_err = "adaptive: mtsg_render_samples has no fixed shape under a per-pixel sample count"; return MTSG_ERR_INVALID; }
+    if (win) { g_err = "adaptive: the tile-window entries are not offered (use mtsg_render / mtsg_render_device)"; return MTSG_ERR_INVALID; }
+    if (s->samplerType != MTSG_SAMPLER_INDEPENDENT) {
+        g_err = "The error-controlling integrator should only be used in conjunction with the independent sampler";
+        return MTSG_ERR_INVALID;
+    }
+    if (p->spp != d.base_count) { g_err = "adaptive: params.spp must equal the descriptor's base_count"; return MTSG_ERR_INVALID; }
+    int rc;
+    if ((rc = set_device(s)) != MTSG_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t N = d.base_count, cap = adaptive_cap(d.max_sample_factor, N);
+    int32_t row0, rows;
+    if (!adaptive_prepass_rows((uint64_t)s->cam.film_w * s->cam.film_h, cap, row0, rows)) {
+        g_err = "adaptive: film size x sample cap leaves no sample ids for the pre-pass";
+        return MTSG_ERR_INVALID;
+    }
+    // the call's tiles: its share of the deal, or the listed keys
+    RenderPlan plan = plan_render(p->tile_w, p->tile_h, 1u, p->tile_stride, p->tile_offset, (uint32_t)s->tileKeys.size(), PLAN_TILE_SLOTS, 1u, true);
+    for (int32_t k : s->tileKeys)
+        if ((uint32_t)k >= plan.allTiles) { g_err = "tile list: a deal key lies outside the rectangle's tiles"; return MTSG_ERR_INVALID; }
+    std::vector<int32_t> keys(plan.ntiles);
+    for (uint32_t v = 0; v < plan.ntiles; ++v) keys[v] = s->tileKeys.empty() ? (int32_t)(plan.toffset + v * plan.tstride) : s->tileKeys[v];
+    // per-pixel state: status, mean, meanSqr and the parked K x K x CH window
+    const int K = 2 * s->cam.border + 1, KT = K == 5 ? 5 : K <= 3 ? 3 : 9, CH = s->cam.has_alpha ? 5 : 4;
+    const size_t stride = (size_t)plan.allTiles * TILE * TILE;
+    std::vector<void *> allocs;
+    struct Free {
+        std::vector<void *> &a;
+        ~Free() { for (void *q : a) hipFree(q); }
+    } freeAll{allocs};
+    auto alloc = [&](size_t bytes, void **q) -> int {
+        HIP_TRY(hipMalloc(q, bytes));
+        allocs.push_back(*q);
+        return MTSG_OK;
+    };
+    DevAdaptive A{};
+    int32_t *keysDev = nullptr;
+    if ((rc = alloc(stride * sizeof(uint32_t), (void **)&A.status)) != MTSG_OK) return rc;
+    if ((rc = alloc(stride * sizeof(float), (void **)&A.mean)) != MTSG_OK) return rc;
+    if ((rc = alloc(stride * sizeof(float), (void **)&A.meanSqr)) != MTSG_OK) return rc;
+    if ((rc = alloc(stride * sizeof(float) * KT * KT * CH, (void **)&A.win)) != MTSG_OK) return rc;
+    if ((rc = alloc(plan.allTiles * sizeof(uint32_t), (void **)&A.tileActive)) != MTSG_OK) return rc;
+    if ((rc = alloc(plan.allTiles * sizeof(int32_t), (void **)&keysDev)) != MTSG_OK) return rc;
+    HIP_TRY(hipMemsetAsync(A.status, 0, stride * sizeof(uint32_t), s->stream));
+    HIP_TRY(hipMemsetAsync(A.tileActive, 0, plan.allTiles * sizeof(uint32_t), s->stream));
+    A.stride = stride;
+    A.maxError = d.max_error;
+    A.quantile = d.quantile;
+    A.baseCount = N;
+    A.limit = (uint32_t)std::min<uint64_t>((uint64_t)std::max(d.max_sample_factor, 0) * N, cap);
+    const uint32_t maxPaths = fit_paths(s, PATH_STATE_BYTES + (s->LP[0].orderBuf ? PATH_ORDER_BYTES : 0) + (s->LP[0].preBuf ? PATH_PRE_BYTES : 0));
+    // the pre-pass strip: 16 columns, one sample per "pixel", ids past the film's
+    const uint32_t preTiles = ((uint32_t)rows + TILE - 1) / TILE;
+    const DevBatch preB{0, row0, TILE, rows, 1, 0, (int)preTiles, 1, 0, PLAN_DEAL_SKEW, 0u, 1u, preTiles * (uint32_t)(TILE * TILE), nullptr,
+                        s->cam.lens ? 1u : 0u};
+    // the largest round batch, for the path state
+    // (a later round lists fewer tiles and may cut them into larger groups than
+    // the first: what bounds every batch is the lane's budget and the round itself)
+    uint32_t s0, ns, need = preB.nslots;
+    const uint64_t lanePaths = std::max<uint64_t>(PLAN_TILE_SLOTS, std::min<uint64_t>(maxPaths, PLAN_MAX_RAYS));
+    for (uint32_t r = 0; r < 2 && adaptive_round(N, cap, s->adaptiveRound, r, s0, ns); ++r)
+        need = std::max<uint32_t>(need, (uint32_t)std::min<uint64_t>(lanePaths, (uint64_t)plan.ntiles * ns * PLAN_TILE_SLOTS));
+    if ((rc = ensure_batch(s, need, 1)) != MTSG_OK) return rc;
+    // the sample id's stride is the cap: sample s of a pixel is sample s of
+    // the plain `path` render with spp = cap
+    DevIntegrator I{p->max_depth, p->rr_depth, p->strict_normals, p->hide_emitters, cap, p->seed, (uint32_t)s->cam.film_w, make_sampler(s, cap)};
+    DevIntegrator Ipre = I;
+    Ipre.spp = 1;
+    Ipre.film_w = TILE;
+    memset(&s->stats, 0, sizeof(s->stats));
+    s->wtLaunches = 0;
+    if ((s->flags & MTSG_FLAG_WAVETIME) && !s->waveTimes)
+        HIP_TRY(hipMalloc((void **)&s->waveTimes, (size_t)WT_WORDS * s->traceGrid * WT_MAX_LAUNCHES * sizeof(unsigned long long)));
+    s->evUsed = 0;
+    s->timed.clear();
+    const bool count = (s->flags & MTSG_FLAG_COUNT) != 0;
+    if (count) HIP_TRY(hipMemsetAsync(s->LP[0].ctr, 0, CTR_WORDS * sizeof(unsigned long long), s->stream));
+    // the differentials are always carried: bounce 0 would recompute them with
+    // the sample-id stride, which is not their scale here
+    // (for this call only: the guard puts the handle's mode back on every way out)
+    struct KeepDiffs {
+        mtsg_scene *s;
+        int diffs, envDiffs, camDiffs;
+        explicit KeepDiffs(mtsg_scene *sc) : s(sc), diffs(sc->ds.cam_diffs), envDiffs(sc->ds.cam_env_diffs), camDiffs(sc->cam.diffs) {}
+        ~KeepDiffs() {
+            s->ds.cam_diffs = diffs;
+            s->ds.cam_env_diffs = envDiffs;
+            s->cam.diffs = camDiffs;
+        }
+    } keepDiffs(s);
+    if (s->hasEnvmap) {
+        s->ds.cam_diffs = 1;
+        s->ds.cam_env_diffs = 0;
+        s->cam.diffs = 1;
+    }
+    s->adaptiveHave = false;
+    s->adaptiveResult = mtsg_adaptive_result{};
+    s->adaptiveResult.quantile = d.quantile;
+    s->adaptiveResult.width = p->tile_w;
+    s->adaptiveResult.height = p->tile_h;
+    plan.lanes = 1;
+    RenderRun R{s, p, I, std::move(plan), film, 0, false, t0};
+    R.count = count;
+    R.blockW = p->tile_w + 2 * s->cam.border;
+    R.blockH = p->tile_h + 2 * s->cam.border;
+    R.maxBounces = p->max_depth > 0 ? p->max_depth : 1 << 30;
+    R.useFinish = s->finishPaths > 0 && !count && !s->knobs;
+    R.adaptive = true;
+    R.adv = A;
+    rc = R.open_lanes();
+    if (rc == MTSG_OK) rc = R.run_adaptive(std::move(keys), keysDev, maxPaths, Ipre, preB, s->adaptiveRound);
+    rc = R.finish(rc);
+    s->adaptiveHave = rc == MTSG_OK;
+    return rc;
+}
+
 // the checks and sizing of a render call, then its RenderRun
 int render_impl(mtsg_scene *s, const mtsg_render_params *p, float *film, int win = 0, bool multi = false) {
     int rc;
     if ((rc = validate(p, s)) != MTSG_OK) return rc;
+    if (s->adaptiveOn) return render_adaptive(s, p, film, win, multi);
     // a handle with a multichannel child set renders through the *_multi
     // entries only (3m + 2 floats per texel), a plain handle through the others
     if (s->aovOn && !multi) {
@@ -1755,6 +2009,10 @@ int mtsg_set_option(mtsg_scene *s, int32_t key, int64_t value) {
             if (value < 0 || value > 1) { g_err = "MTSG_OPT_LEAF_FILTER: 0 (the setup mode steps over rectangle records) or 1 (its leaves hold none)"; return MTSG_ERR_INVALID; }
             s->leafFilterOpt = value != 0;
             return MTSG_OK;
+        case MTSG_OPT_ADAPTIVE_ROUND:
+            if (value < 0 || value > (int64_t)ADAPTIVE_MAX_ROUND) { g_err = "MTSG_OPT_ADAPTIVE_ROUND: 0 (the base count) or 1..65536 samples per later round"; return MTSG_ERR_INVALID; }
+            s->adaptiveRound = (uint32_t)value;
+            return MTSG_OK;
         default:
             g_err = "unknown option key " + std::to_string(key);
             return MTSG_ERR_INVALID;
@@ -1930,6 +2188,30 @@ int mtsg_scene_set_direct(mtsg_scene *s, const mtsg_direct_desc *d) {
     if (d->ao_samples && !(d->ao_ray_length > 0)) { g_err = "ao: rayLength must be greater than zero (mtsh_scene_direct resolves the default)"; return MTSG_ERR_INVALID; }
     s->direct = *d;
     s->directOn = true;
+    return MTSG_OK;
+}
+
+int mtsg_scene_set_adaptive(mtsg_scene *s, const mtsg_adaptive_desc *d) {
+    if (!s) { g_err = "null scene"; return MTSG_ERR_INVALID; }
+    if (!d) { s->adaptiveOn = false; s->adaptive = mtsg_adaptive_desc{}; return MTSG_OK; }
+    // adaptive.cpp:176-178, and this project's own refusal of the unbounded mode
+    if (d->base_count < 8) { g_err = "Starting the adaptive integrator with less than 8 samples per pixel does not make much sense -- giving up."; return MTSG_ERR_INVALID; }
+    if (d->max_sample_factor < 0) { g_err = "adaptive: max_sample_factor must not be negative: a bound on the samples per pixel is required"; return MTSG_ERR_INVALID; }
+    if ((uint64_t)d->max_sample_factor * d->base_count > (1u << 24)) { g_err = "adaptive: max_sample_factor x base_count exceeds 2^24 samples per pixel"; return MTSG_ERR_INVALID; }
+    if (!(d->max_error >= 0.0f) || !(d->quantile >= 0.0f)) { g_err = "adaptive: max_error and quantile must not be negative"; return MTSG_ERR_INVALID; }
+    s->adaptive = *d;
+    s->adaptiveOn = true;
+    return MTSG_OK;
+}
+
+int mtsg_adaptive_info(mtsg_scene *s, mtsg_adaptive_result *out, uint32_t *counts, size_t capacity) {
+    if (!s || !out) { g_err = "null argument"; return MTSG_ERR_INVALID; }
+    if (!s->adaptiveHave) { g_err = "mtsg_adaptive_info: the handle has rendered no adaptive scene"; return MTSG_ERR_INVALID; }
+    *out = s->adaptiveResult;
+    if (counts) {
+        if (capacity < s->adaptiveCounts.size()) { g_err = "mtsg_adaptive_info: counts holds fewer than tile_w x tile_h entries"; return MTSG_ERR_INVALID; }
+        memcpy(counts, s->adaptiveCounts.data(), s->adaptiveCounts.size() * sizeof(uint32_t));
+    }
     return MTSG_OK;
 }
 

@@ -944,6 +944,7 @@ void SceneBuilder::integrator(const std::string &type, const Properties &props, 
     }
     const std::string t = lower(type);
     if (t == "multichannel") { multichannel(props, line); return; }
+    if (t == "adaptive") { adaptive(props, line); return; }
     if (t == "direct") {
         // MIDirectIntegrator(props) (direct.cpp:93-108): shadingSamples is the
         // shorthand for both counts
@@ -971,7 +972,7 @@ void SceneBuilder::integrator(const std::string &type, const Properties &props, 
         return;
     }
     if (t != "path")
-        throw err(at(line) + "integrator \"" + t + "\" is outside this build's scope (only 'path', 'direct', 'ao', 'multichannel' and 'myPath2_OM')");
+        throw err(at(line) + "integrator \"" + t + "\" is outside this build's scope (only 'path', 'direct', 'ao', 'multichannel', 'adaptive' and 'myPath2_OM')");
     // MonteCarloIntegrator(props) (integrator.cpp:199-234)
     ip = IntegratorProps();
     ip.type = t;
@@ -1027,6 +1028,39 @@ void SceneBuilder::multichannel(const Properties &, int line) {
     ip.type = "path";   // the render parameters of its `path` child (the defaults without one)
     ip.multichannel = true;
     ip.children = pendingChildren;
+    scene.integrator = ip;
+    pendingChildren.clear();
+    havePendingPath = false;
+}
+
+// The child of `adaptive` (AdaptiveIntegrator::addChild, adaptive.cpp:94-104,
+// takes any SamplingIntegrator; this build `path`)
+int SceneBuilder::adaptiveChild(const std::string &type, const Properties &props, int line) {
+    const std::string t = type == "myPath2_OM" ? type : lower(type);
+    if (t != "path")
+        throw err(at(line) + "adaptive: child integrator \"" + t + "\" is outside this build's scope (only 'path')");
+    return integratorChild(t, props, line);
+}
+
+// AdaptiveIntegrator(props) (adaptive.cpp:70-81) around the child added before
+// it, the way multichannel's children are
+void SceneBuilder::adaptive(const Properties &props, int line) {
+    if (pendingChildren.empty()) throw err(at(line) + "No sub-integrator was specified!");   // adaptive.cpp:115-116
+    if (pendingChildren.size() != 1 || !havePendingPath)
+        throw err(at(line) + "adaptive: a child integrator other than one 'path' is outside this build's scope");
+    IntegratorProps ip = pendingPath;
+    ip.type = "path";   // the render parameters of its `path` child
+    ip.adaptive = true;
+    ip.adMaxError = props.getFloat("maxError", 0.05f);
+    ip.adMaxSampleFactor = (int)props.getInt("maxSampleFactor", 32);
+    ip.adPValue = props.getFloat("pValue", 0.05f);
+    // the reference reads a negative factor as infinity (adaptive.cpp:73-77): a
+    // render without a bound is this project's own error
+    if (ip.adMaxSampleFactor < 0)
+        throw err(at(line) + "adaptive: 'maxSampleFactor' must not be negative: a bound on the samples per pixel is required "
+                             "(the reference's unbounded mode is not offered)");
+    if (!(ip.adPValue > 0.0f && ip.adPValue < 1.0f)) throw err(at(line) + "adaptive: 'pValue' must lie in (0, 1)");
+    if (!(ip.adMaxError >= 0.0f)) throw err(at(line) + "adaptive: 'maxError' must not be negative");
     scene.integrator = ip;
     pendingChildren.clear();
     havePendingPath = false;
@@ -1246,9 +1280,73 @@ void SceneBuilder::finish(const mtsh_scene_overrides *ov) {
             throw err("request2DArray(): Not supported for the Hammersley QMC sequence! If you used this sampler together with the "
                       "'direct' or 'ao' integrators, you will have to set the 'shadingSamples' parameter to 1 to use this sampler.");
     }
+    if (scene.integrator.adaptive) {
+        // AdaptiveIntegrator::preprocess and renderBlock (adaptive.cpp:119-121,176-178)
+        if (scene.sampler.type != MTSG_SAMPLER_INDEPENDENT)
+            throw err("The error-controlling integrator should only be used in conjunction with the independent sampler");
+        if (scene.sampleCount < 8)
+            throw err("Starting the adaptive integrator with less than 8 samples per pixel does not make much sense -- giving up.");
+        if ((int64_t)scene.integrator.adMaxSampleFactor * scene.sampleCount > (int64_t)1 << 24)
+            throw err("adaptive: 'maxSampleFactor' x sampleCount exceeds 2^24 samples per pixel");
+    }
     scene.finalize();
     scene.buildAov();
     scene.buildDirect();
+    scene.buildAdaptive();
+}
+
+namespace {
+// The standard normal quantile in double: Wichura, Algorithm AS 241 (Applied
+// Statistics 37, 1988), routine PPND16, about 1e-16 relative accuracy
+double normalQuantile(double p) {
+    const double q = p - 0.5;
+    if (std::fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        const double num = (((((((2.5090809287301226727e3 * r + 3.3430575583588128105e4) * r + 6.7265770927008700853e4) * r +
+                                4.5921953931549871457e4) * r + 1.3731693765509461125e4) * r + 1.9715909503065514427e3) * r +
+                              1.3314166789178437745e2) * r + 3.3871328727963666080e0);
+        const double den = (((((((5.2264952788528545610e3 * r + 2.8729085735721942674e4) * r + 3.9307895800092710610e4) * r +
+                                2.1213794301586595867e4) * r + 5.3941960214247511077e3) * r + 6.8718700749205790830e2) * r +
+                              4.2313330701600911252e1) * r + 1.0);
+        return q * num / den;
+    }
+    double r = q < 0 ? p : 1.0 - p;
+    r = std::sqrt(-std::log(r));
+    double v;
+    if (r <= 5.0) {
+        r -= 1.6;
+        const double num = (((((((7.74545014278341407640e-4 * r + 2.27238449892691845833e-2) * r + 2.41780725177450611770e-1) * r +
+                                1.27045825245236838258e0) * r + 3.64784832476320460504e0) * r + 5.76949722146069140550e0) * r +
+                              4.63033784615654529590e0) * r + 1.42343711074968357734e0);
+        const double den = (((((((1.05075007164441684324e-9 * r + 5.47593808499534494600e-4) * r + 1.51986665636164571966e-2) * r +
+                                1.48103976427480074590e-1) * r + 6.89767334985100004550e-1) * r + 1.67638483018380384940e0) * r +
+                              2.05319162663775882187e0) * r + 1.0);
+        v = num / den;
+    } else {
+        r -= 5.0;
+        const double num = (((((((2.01033439929228813265e-7 * r + 2.71155556874348757815e-5) * r + 1.24266094738807843860e-3) * r +
+                                2.65321895265761230930e-2) * r + 2.96560571828504891230e-1) * r + 1.78482653991729133580e0) * r +
+                              5.46378491116411436990e0) * r + 6.65790464350110377720e0);
+        const double den = (((((((2.04426310338993978564e-15 * r + 1.42151175831644588870e-13) * r + 1.84631831751005468180e-11) * r +
+                                7.86869131145613259100e-9) * r + 1.48753612908506148525e-7) * r + 1.36929880922735805310e-4) * r +
+                              5.99832206555887937690e-4) * r + 1.0);
+        v = num / den;
+    }
+    return q < 0 ? -v : v;
+}
+}  // namespace
+
+// The adaptive descriptor beside the scene descriptor (mtsg.h
+// mtsg_adaptive_desc): the properties, the sampler's sampleCount and
+// m_quantile = (Float) quantile(normal(0, 1), 1 - pValue / 2) (adaptive.cpp:161-162;
+// the reference's Float pValue widens to double there)
+void Scene::buildAdaptive() {
+    memset(&adaptiveDesc, 0, sizeof(adaptiveDesc));
+    if (!integrator.adaptive) return;
+    adaptiveDesc.max_error = integrator.adMaxError;
+    adaptiveDesc.quantile = (float)normalQuantile(1.0 - (double)integrator.adPValue / 2.0);
+    adaptiveDesc.max_sample_factor = integrator.adMaxSampleFactor;
+    adaptiveDesc.base_count = (uint32_t)sampleCount;
 }
 
 // The direct / ao descriptor beside the scene descriptor (mtsg.h

@@ -298,6 +298,12 @@ int mtsh_scene_direct(const mtsh_scene *s, mtsg_direct_desc *out) {
     return 1;
 }
 
+int mtsh_scene_adaptive(const mtsh_scene *s, mtsg_adaptive_desc *out) {
+    if (!s || !s->scene->integrator.adaptive) return 0;
+    if (out) *out = s->scene->adaptiveDesc;
+    return 1;
+}
+
 int mtsh_scene_film_formats(const mtsh_scene *s, int32_t *formats, int capacity) {
     try {
         std::vector<std::string> ch;

@@ -851,13 +851,21 @@ struct Loader {
                 parseProps(c, props, nested);
                 // multichannel's nested integrators, in document order
                 // (MultiChannelIntegrator::addChild, multichannel.cpp:219-231)
+                // ... and adaptive's one (AdaptiveIntegrator::addChild, adaptive.cpp:94-104)
+                const bool adaptive = lower(c.attr("type")) == "adaptive";
                 for (XNode *k : nested) {
                     substAll(*k);
-                    if (k->tag != "integrator" || lower(c.attr("type")) != "multichannel")
+                    if (k->tag != "integrator" || (lower(c.attr("type")) != "multichannel" && !adaptive))
                         throw err("line " + std::to_string(k->line) + ": unsupported element <" + k->tag + "> inside this <integrator>");
                     Properties kp;
                     std::vector<XNode *> kn;
                     parseProps(*k, kp, kn);
+                    if (adaptive) {
+                        if (!kn.empty() && lower(k->attr("type")) == "path")
+                            throw err("line " + std::to_string(k->line) + ": adaptive: a child integrator with nested objects is not supported");
+                        B.adaptiveChild(k->attr("type"), kp, k->line);
+                        continue;
+                    }
                     if (!kn.empty() && lower(k->attr("type")) != "multichannel")
                         throw err("line " + std::to_string(k->line) + ": multichannel: a child integrator with nested objects is not supported");
                     B.integratorChild(k->attr("type"), kp, k->line);

@@ -170,6 +170,18 @@ int mtsh_path_job_create(const mtsh_scene *scene, int n_gpus, mtsh_path_job **ou
                 return rcd;
             }
         }
+        // an adaptive scene: its parameters on every GPU.  A pixel belongs to one
+        // tile, so the GPUs' shares sum as the plain film's do, and every GPU
+        // computes the same pre-pass luminance
+        mtsg_adaptive_desc ad;
+        if (mtsh_scene_adaptive(scene, &ad)) {
+            const int rcd = mtsg_scene_set_adaptive(job->handles[g], &ad);
+            if (rcd != MTSG_OK) {
+                g_perr = "GPU " + std::to_string(g) + ": " + device_error();
+                mtsh_path_job_destroy(job);
+                return rcd;
+            }
+        }
     }
     *out = job;
     return MTSG_OK;

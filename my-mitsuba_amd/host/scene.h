@@ -145,6 +145,11 @@ struct IntegratorProps {
     // Scene::buildDirect
     int emitterSamples = 1, bsdfSamples = 1, aoSamples = 1;
     float aoRayLength = -1.0f;
+    // adaptive (adaptive.cpp:70-81) around a `path` child, whose properties
+    // are the ones above (type stays "path")
+    bool adaptive = false;
+    float adMaxError = 0.05f, adPValue = 0.05f;
+    int adMaxSampleFactor = 32;
 };
 
 struct KDBuildParams {                // gkdtree.h:734-744 defaults, except stopPrims
@@ -230,6 +235,9 @@ struct Scene {
     // direct / ao scenes (buildDirect): the descriptor beside `desc`
     mtsg_direct_desc directDesc{};
     void buildDirect();
+    // adaptive scenes (buildAdaptive): the descriptor beside `desc`
+    mtsg_adaptive_desc adaptiveDesc{};
+    void buildAdaptive();
 
     std::vector<uint8_t> triGrouped;  // triangle lives in a shape group's own tree (two-level)
 
@@ -334,6 +342,10 @@ public:
     // then the parent, which takes the children added so far
     int integratorChild(const std::string &type, const Properties &props, int line = 0);
     void multichannel(const Properties &props, int line = 0);
+    // the child of an `adaptive` integrator whose parent is already known (the
+    // XML route): `path` only, kept like multichannel's until the parent is set
+    int adaptiveChild(const std::string &type, const Properties &props, int line = 0);
+    void adaptive(const Properties &props, int line = 0);
     void sensor(const std::string &type, const Properties &props, int line = 0);
     void film(const std::string &type, const Properties &props);
     void rfilter(const std::string &type, const Properties &props);

@@ -38,6 +38,7 @@ MTSG_OPT_CAMERA_DIFFS = 7
 MTSG_OPT_RECT_SETUP = 8
 MTSG_OPT_RAY_PRESETUP = 9
 MTSG_OPT_LEAF_FILTER = 10
+MTSG_OPT_ADAPTIVE_ROUND = 11   # mtsg_set_option: samples per pixel of an adaptive render's later rounds
 MTSG_RECT_SETUP_CAP = 8  # most rectangles of a flat scene for MTSG_OPT_RECT_SETUP 1 to apply
 # mtsg_render_params.integrator
 MTSG_INTEGRATOR_PATH = 0
@@ -294,6 +295,18 @@ class DirectDesc(C.Structure):
                 ("ao_ray_length", C.c_float)]
 
 
+class AdaptiveDesc(C.Structure):
+    """mtsg_adaptive_desc (include/mtsg.h): the `adaptive` integrator's parameters beside the scene descriptor."""
+    _fields_ = [("max_error", C.c_float), ("quantile", C.c_float), ("max_sample_factor", C.c_int32),
+                ("base_count", C.c_uint32)]
+
+
+class AdaptiveResult(C.Structure):
+    """mtsg_adaptive_result (include/mtsg.h): what the last adaptive render of a handle found."""
+    _fields_ = [("average_luminance", C.c_float), ("quantile", C.c_float), ("total_samples", C.c_uint64),
+                ("width", C.c_int32), ("height", C.c_int32), ("rounds", C.c_uint32), ("luminance_variance", C.c_float)]
+
+
 class DigestEntry(C.Structure):
     """mtsh_digest_entry."""
     _fields_ = [("name", C.c_char * 32), ("bytes", C.c_uint64), ("hash", C.c_uint64)]
@@ -316,6 +329,7 @@ DEVICE_SYMBOLS = [
     "mtsg_debug_stragglers", "mtsg_set_test_knobs", "mtsg_set_option",
     "mtsg_scene_set_aov", "mtsg_render_multi", "mtsg_render_device_multi", "mtsg_render_device_tiles_multi",
     "mtsg_render_samples_multi", "mtsg_scene_set_direct", "mtsg_scene_kernel_sets", "mtsg_bsdf_query",
+    "mtsg_scene_set_adaptive", "mtsg_adaptive_info",
 ]
 HOST_SYMBOLS = [
     "mtsh_scene_load", "mtsh_scene_load_overrides", "mtsh_scene_load_props", "mtsh_scene_set_scene_props", "mtsh_set_kd_threads", "mtsh_set_instancing", "mtsh_scene_desc", "mtsh_scene_render_params",
@@ -327,6 +341,7 @@ HOST_SYMBOLS = [
     "mtsh_scene_set_sampler", "mtsh_scene_set_integrator", "mtsh_scene_finish", "mtsh_scene_abort", "mtsh_scene_digest",
     "mtsh_scene_add_integrator_child", "mtsh_scene_set_multichannel", "mtsh_scene_aov", "mtsh_scene_film_formats",
     "mtsh_scene_film_channels", "mtsh_develop_multi", "mtsh_write_exr", "mtsh_scene_direct",
+    "mtsh_scene_adaptive",
 ]
 PATH_SYMBOLS = [
     "mtsh_path_job_create", "mtsh_path_job_gpus", "mtsh_path_job_render", "mtsh_path_job_cancel",
@@ -437,6 +452,8 @@ def host_lib() -> C.CDLL:
         lib.mtsh_scene_aov.argtypes = [C.c_void_p]
         lib.mtsh_scene_direct.restype = C.c_int
         lib.mtsh_scene_direct.argtypes = [C.c_void_p, C.POINTER(DirectDesc)]
+        lib.mtsh_scene_adaptive.restype = C.c_int
+        lib.mtsh_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveDesc)]
         lib.mtsh_scene_film_formats.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
         lib.mtsh_scene_film_channels.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.mtsh_develop_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p]
@@ -487,6 +504,9 @@ def device_lib() -> C.CDLL:
         lib.mtsg_render_samples.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p]
         lib.mtsg_scene_set_aov.argtypes = [C.c_void_p, C.POINTER(AovDesc)]
         lib.mtsg_scene_set_direct.argtypes = [C.c_void_p, C.POINTER(DirectDesc)]
+        if hasattr(lib, "mtsg_scene_set_adaptive"):   # (as above; GPUScene.set_adaptive then raises)
+            lib.mtsg_scene_set_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveDesc)]
+            lib.mtsg_adaptive_info.argtypes = [C.c_void_p, C.POINTER(AdaptiveResult), C.c_void_p, C.c_size_t]
         for fn in ("mtsg_render_multi", "mtsg_render_device_multi", "mtsg_render_device_tiles_multi",
                    "mtsg_render_samples_multi"):
             getattr(lib, fn).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p]
@@ -635,6 +655,11 @@ class Scene:
         """The sample counts of a `direct` or `ao` scene (mtsh_scene_direct), None for other integrators."""
         d = DirectDesc()
         return d if host_lib().mtsh_scene_direct(self._h, C.byref(d)) else None
+
+    def adaptive(self) -> "AdaptiveDesc | None":
+        """The parameters of an `adaptive` scene (mtsh_scene_adaptive), None for other integrators."""
+        d = AdaptiveDesc()
+        return d if host_lib().mtsh_scene_adaptive(self._h, C.byref(d)) else None
 
     def textures(self) -> list:
         """The scene's bitmap texture headers (TextureHeader)."""
@@ -987,6 +1012,27 @@ class GPUScene:
         # ... and so are the sample counts of a direct / ao scene
         if getattr(scene, "direct", None) is not None and scene.direct() is not None:
             self.set_direct(scene.direct())
+        # ... and the parameters of an adaptive one
+        if getattr(scene, "adaptive", None) is not None and scene.adaptive() is not None:
+            self.set_adaptive(scene.adaptive())
+
+    def set_adaptive(self, desc: "AdaptiveDesc | None") -> None:
+        """Give the handle the `adaptive` integrator's parameters (mtsg_scene_set_adaptive): its `path`
+        renders then sample every pixel until its error test passes; None removes them."""
+        self._check(device_lib().mtsg_scene_set_adaptive(self._h, C.byref(desc) if desc is not None else None),
+                    "mtsg_scene_set_adaptive")
+
+    def adaptive_info(self, params: RenderParams) -> dict:
+        """The last adaptive render (mtsg_adaptive_info): average_luminance, luminance_variance, quantile, total_samples, rounds
+        and counts, the (tile_h, tile_w) uint32 map of the samples every pixel took."""
+        r = AdaptiveResult()
+        counts = np.zeros((params.tile_h, params.tile_w), np.uint32)
+        self._check(device_lib().mtsg_adaptive_info(self._h, C.byref(r), _ptr(counts), counts.size), "mtsg_adaptive_info")
+        if (r.height, r.width) != counts.shape:
+            raise RuntimeError("adaptive_info: the last adaptive render took another rectangle")
+        return {"average_luminance": np.float32(r.average_luminance), "quantile": np.float32(r.quantile),
+                "total_samples": int(r.total_samples), "rounds": int(r.rounds),
+                "luminance_variance": float(r.luminance_variance), "counts": counts}
 
     def set_direct(self, desc: "DirectDesc | None") -> None:
         """Give the handle the sample counts of `direct` / `ao` renders (mtsg_scene_set_direct); None removes them."""
@@ -1284,5 +1330,6 @@ class PathJob:
         self.close()
 
 
+MTSG_ERR_INVALID = -1
 MTSG_ERR_CANCELLED = -4
 MTSG_ERR_TRAVERSAL = -6
